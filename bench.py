@@ -22,6 +22,12 @@ A step = VC.pipeline on the step's clip(s) as SURVEY.md 8(d) defines the metric:
 host memory), every kernel, D2H of the int16 PCM -- all inside the timed region.
 Weak scaling (c2 / c3): every rank converts its own clip(s) per step; value = all ranks' audio seconds / max-rank wall
 (whole-job aggregate, as the driver contract asks; value_per_gpu = value / n_gpus).  c5 is strong scaling.
+
+A plain run sets up, warms up, times --steps steps and prints the result line, nothing more.  --full adds what the
+headline does not need: the child benches (exact fp32, outliers, decoder outliers, 95 s clip, full decoder, c3, c5), the
+sustained loop, the serial roofline step and the CPU oracle baseline.  --dump-outputs DIR writes the int16 PCM the last
+timed step returned (as float32 .npy, a seeded sample where the whole exceeds DUMP_BUDGET_BYTES) for output-for-output
+comparison of two builds: the inputs are seeded, so the same arguments give the same inputs on every run.
 """
 import argparse
 import json
@@ -52,6 +58,7 @@ C5_UTTERANCES = 256
 CPU_SAMPLE_SECONDS = 30.0    # the clip the metric is quoted on (attention is O(T^2): a shorter sample would flatter the CPU)
 PMC_FILES = ("pmc_traffic_r06.json", "pmc_traffic_r05.json", "pmc_traffic_r04.json", "pmc_traffic_r03.json")     # newest first
 WORKER_DEADLINE_S = 3600.0   # launch_workers: the whole multi-rank run
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: all files together
 # algorithmic HBM bytes of one launch of the dominant kernel (fused ResBlock step, NSF stage 2 of a 32 s chunk at 48 k:
 # C = 128 channels x 383 760 positions x 4 B, read x once + write y once); DESIGN.md "Algorithmic work per unit"
 DOM_ALGO_BYTES_PER_LAUNCH = 2 * 128 * 383760 * 4
@@ -117,6 +124,26 @@ def c5_lengths():
     """BASELINE configs[4]'s stand-in for TTS utterances: 256 lengths U(3, 15) s, whole 10 ms frames."""
     g = np.random.Generator(np.random.PCG64(5))
     return [int(round(s * 100)) * 160 for s in g.uniform(3.0, 15.0, C5_UTTERANCES)]
+
+
+def dump_arrays(pcms, ids, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: {file name: array} of the int16 PCM each utterance returned (float32 holds int16 exactly), named
+    by utterance id, plus `pcm_lengths`.  When the whole does not fit the budget, every utterance keeps the same share of
+    its samples at positions drawn from a generator seeded by its id, stored beside it (`_at`, float64)."""
+    lens = [int(p.shape[0]) for p in pcms]
+    out = {"pcm_lengths": np.asarray(lens, np.float64)}
+    room = budget - 8 * len(lens) - 128 * (1 + 2 * len(lens))      # the lengths and every .npy header
+    full = 4 * sum(lens) <= room
+    keep = 1.0 if full else room / (12.0 * sum(lens))               # 4 B value + 8 B position per kept sample
+    for i, p in zip(ids, pcms):
+        name = f"pcm_{i:03d}"
+        if full:
+            out[name] = p.astype(np.float32)
+        else:
+            at = np.sort(np.random.default_rng(i).choice(p.shape[0], int(p.shape[0] * keep), replace=False))
+            out[name] = p[at].astype(np.float32)
+            out[name + "_at"] = at.astype(np.float64)
+    return out
 
 
 def cpu_baseline():
@@ -209,7 +236,7 @@ def child_bench(extra_args, env_extra, label, roofline=True):
     """One more bench of this run in a FRESH child process, started before this process touches the GPU and run to
     completion (never an exec of a GPU-initialised process, never two benches sharing the device)."""
     env = dict(os.environ, **env_extra)
-    cmd = [sys.executable, os.path.abspath(__file__)] + extra_args + ["--no-cpu-baseline", "--no-children"]
+    cmd = [sys.executable, os.path.abspath(__file__)] + extra_args + ["--full", "--no-cpu-baseline", "--no-children"]
     if not roofline:
         cmd.append("--no-roofline")
     try:
@@ -390,10 +417,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="clips per step (c3 default 64, c2 default 1)")
     ap.add_argument("--f0-method", choices=["rmvpe+", "fcpe", "mangio-crepe"], default="rmvpe+",
                     help="F0 back-end of VC.get_f0; BASELINE's metric is quoted on rmvpe+ (the others: secondary lines)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: child benches, sustained loop, roofline step, CPU baseline (off by default)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the PCM of the last timed step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--no-children", "--no-exact-fp32", dest="no_children", action="store_true",
-                    help="skip the exact_fp32 and c3 child benches of the default run")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="with --full: skip the child benches")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the sustained loop and roofline step")
     ap.add_argument("--profile-out", default="")
     ap.add_argument("--hubert-outliers", action="store_true",
                     help="HuBERT with planted massive-activation units (what real ContentVec-shaped weights do to the range guard)")
@@ -411,6 +442,10 @@ def main():
     B = a.batch or (C3_BATCH if c3 else 1)
     if a.steps is None:
         a.steps = 3 if (c3 or c5) else 10
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:
+        a.no_children = a.no_roofline = a.no_cpu_baseline = True
 
     rank, local, world = D.env_rank()
     if world != a.gpus and world > 1:
@@ -480,10 +515,12 @@ def main():
     outs = [torch.empty(ctx.out_capacity(m, c.shape[0], params), dtype=torch.int16).pin_memory()
             for c, m in zip(clips, model_of)]
     calls = []                                            # one convert_batch call per resident voice model
+    order = []                                            # the clip behind each entry of step()'s result
     for m in sorted(set(model_of)):
         sel = [i for i, mm in enumerate(model_of) if mm == m]
         calls.append((m, [wavs[i].data_ptr() for i in sel], [clips[i].shape[0] for i in sel],
                       [outs[i].data_ptr() for i in sel]))
+        order += sel
     n = clips[0].shape[0]
     torch.cuda.synchronize()
 
@@ -506,6 +543,13 @@ def main():
     ms_per_step = dt / a.steps * 1e3
     rtf = a.steps * audio_seconds_per_step / dt
     stage = ctx.last_timing()
+    if a.dump_outputs and rank == 0:
+        # what the last timed step handed back (the outs buffers are reused by the untimed steps of --full below)
+        ids = [mine[i] for i in order] if c5 else order
+        arrays = dump_arrays([outs[i][:k].numpy() for i, k in zip(order, got)], ids)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in arrays.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), arr)
     # The headline's timed region (steps x ~26 ms) ends inside the few hundred milliseconds the boxes of this pool hold their
     # boost clock (DESIGN.md "What sustained load does").  For the record, NOT the headline: the same step 80 more times
     # (~2 s of uninterrupted load), reported as `sustained`.
