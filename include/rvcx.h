@@ -242,6 +242,11 @@ int64_t rvcx_bucket_length(rvcx_ctx*, int model_id, int64_t n, const rvcx_params
 /* Member counts of the micro-batches the last rvcx_convert_batch* call of this context formed (in launch order);
  * returns their number (counts receives at most cap of them). */
 int rvcx_last_micro_batches(rvcx_ctx*, int32_t* counts, int cap);
+/* The cut points (the reference's opt_ts, pipeline.py:329-344: sample indices of the filtered clip) the last
+ * rvcx_convert_batch* call of this context cut each utterance at, in the caller's order: for every utterance its count,
+ * then that many points (an uncut clip: 0 and nothing).  Returns the number of values of the whole list (out receives at
+ * most cap of them), -1 without a context. */
+int64_t rvcx_last_cuts(rvcx_ctx*, int64_t* out, int64_t cap);
 /* floats of parity noise rvcx_convert_batch consumes for one n-sample utterance: for each
  * chunk in order, z_noise (inter*T) then src_noise (T*upp) -- the draw order of the reference */
 int64_t rvcx_noise_len(rvcx_ctx*, int model_id, int64_t n, const rvcx_params* p);
@@ -424,6 +429,9 @@ int rvcx_op_bigru(rvcx_ctx*, const float* x, const float* w_ih, const float* w_h
                   const float* b_hh_r, float* y, int B, int T, int I, int H);
 /* scipy.signal.filtfilt(bh, ah, x) of pipeline.py:19-22,329 (float64) */
 int rvcx_op_highpass(rvcx_ctx*, const double* x, double* y, int64_t n);
+/* The same filter on the host, serial in scipy's own operation order: bit for bit what scipy.signal.filtfilt returns.
+ * The cut search of rvcx_convert_batch runs on it.  No GPU, no context; n > 18 samples; x and y may alias. */
+int rvcx_highpass_exact(const double* x, double* y, int64_t n);
 
 /* ---- FLAC on the host (csrc/flac.hip; no GPU, no context) -------------------------------------------------------
  * rvc/infer/infer.py:153 writes WAV bytes whatever the extension of output_path; the mirror writes a real FLAC stream when

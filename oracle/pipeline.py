@@ -61,6 +61,32 @@ def chunk_points(audio: np.ndarray, geo: Geometry):
     return opt_ts
 
 
+def cut_margins(audio: np.ndarray, geo: Geometry):
+    """How well chunk_points' choice is conditioned, per cut window (audio already filtered): None for a window of exact
+    zeros (every index ties; the first wins), else min over the indices whose frame (// 160) differs from the chosen one
+    of |audio_sum| / min |audio_sum| (inf when the window holds no other frame; 0 when the minimum itself is 0)."""
+    audio_pad = np.pad(audio, (WINDOW // 2, WINDOW // 2), mode="reflect")
+    if audio_pad.shape[0] <= geo.t_max:
+        return []
+    audio_sum = np.zeros_like(audio)
+    for i in range(WINDOW):
+        audio_sum += audio_pad[i:i - WINDOW]
+    out = []
+    for t in range(geo.t_center, audio.shape[0], geo.t_center):
+        lo = t - geo.t_query
+        seg = np.abs(audio_sum[lo:t + geo.t_query])
+        if not seg.any():
+            out.append(None)
+            continue
+        k = int(np.where(seg == seg.min())[0][0])
+        other = (lo + np.arange(seg.shape[0])) // WINDOW != (lo + k) // WINDOW
+        if seg[k] == 0:
+            out.append(0.0)
+        else:
+            out.append(float(seg[other].min() / seg[k]) if other.any() else float("inf"))
+    return out
+
+
 def f0_to_coarse(f0: np.ndarray, pitch: float, f0_min=50, f0_max=1100, inp_f0=None, x_pad: int = 1):
     """pipeline.py:148-150,183-201.  ``inp_f0``: the (rows, 2) float32 table VC.pipeline parses from an f0 file
     (pipeline.py:349-360), applied exactly as pipeline.py:185-191 does.  Returns (coarse int, f0 Hz)."""

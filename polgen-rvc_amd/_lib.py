@@ -78,11 +78,11 @@ SYMBOLS = [
     "rvcx_load_rmvpe", "rvcx_index_exhaustive", "rvcx_load_crepe", "rvcx_crepe_frames", "rvcx_crepe_predict", "rvcx_op_crepe_decode", "rvcx_get_f0_crepe_x", "rvcx_load_fcpe", "rvcx_fcpe_f0", "rvcx_fcpe_frames", "rvcx_get_f0_fcpe_x", "rvcx_op_fcpe_post", "rvcx_load_synth", "rvcx_unload_synth", "rvcx_load_index", "rvcx_load_index_ivf",
     "rvcx_weights_regions", "rvcx_weights_adopt", "rvcx_weights_clone", "rvcx_rmvpe_f0", "rvcx_rmvpe_frames", "rvcx_rmvpe_mel", "rvcx_synth_infer_taps", "rvcx_hubert_features",
     "rvcx_hubert_frames", "rvcx_synth_infer", "rvcx_synth_infer_window", "rvcx_synth_dec_rf", "rvcx_synth_upp", "rvcx_index_blend",
-    "rvcx_out_len", "rvcx_convert_batch", "rvcx_convert_batch_f64", "rvcx_micro_batch", "rvcx_bucket_length", "rvcx_last_micro_batches", "rvcx_noise_len",
+    "rvcx_out_len", "rvcx_convert_batch", "rvcx_convert_batch_f64", "rvcx_micro_batch", "rvcx_bucket_length", "rvcx_last_micro_batches", "rvcx_last_cuts", "rvcx_noise_len",
     "rvcx_get_f0", "rvcx_get_f0_x", "rvcx_vc", "rvcx_vc_frames", "rvcx_last_timing",
     "rvcx_flop_counter", "rvcx_fp32_reruns", "rvcx_mem_info", "rvcx_conv_profile", "rvcx_conv_profile_csv", "rvcx_stream", "rvcx_op_conv1d", "rvcx_op_resblock_pair", "rvcx_bench_resblock_pair", "rvcx_bench_conv1d", "rvcx_conv_override", "rvcx_op_convtranspose1d",
     "rvcx_op_conv2d3x3", "rvcx_op_convblock2d", "rvcx_op_convtranspose2d", "rvcx_op_attention", "rvcx_op_layernorm_c",
-    "rvcx_op_bigru", "rvcx_op_highpass", "rvcx_convert_batch_ex", "rvcx_get_f0_x_ex", "rvcx_fp32_layers", "rvcx_fp32_pinned",
+    "rvcx_op_bigru", "rvcx_op_highpass", "rvcx_highpass_exact", "rvcx_convert_batch_ex", "rvcx_get_f0_x_ex", "rvcx_fp32_layers", "rvcx_fp32_pinned",
     "rvcx_gru_fallbacks", "rvcx_gru_publish_probe", "rvcx_debug_inject", "rvcx_f0_file_track", "rvcx_op_gemm_tm", "rvcx_op_layernorm_tm",
     "rvcx_resample_len", "rvcx_resample_f64", "rvcx_resample_f64_kind", "rvcx_bench_gemm", "rvcx_device_info",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
@@ -106,6 +106,8 @@ def lib() -> C.CDLL:
         _lib.rvcx_fp32_layers.restype = C.c_int64
         _lib.rvcx_gru_fallbacks.restype = C.c_int64
         _lib.rvcx_bucket_length.restype = C.c_int64
+        _lib.rvcx_last_cuts.restype = C.c_int64
+        _lib.rvcx_last_cuts.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         _lib.rvcx_resample_len.restype = C.c_int64
         _lib.rvcx_noise_len.restype = C.c_int64
         _lib.rvcx_crepe_frames.restype = C.c_int64
@@ -182,6 +184,16 @@ def f0_file_track(inp_f0) -> np.ndarray:
     if n < 0:
         raise RvcxError("f0_file_track: " + (lib().rvcx_last_error(None) or b"").decode())
     return out[:n].copy()
+
+
+def highpass_exact(x) -> np.ndarray:
+    """scipy.signal.filtfilt(bh, ah, x) of pipeline.py:329 on the host, bit for bit (the cut search's filter; no GPU)"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    y = np.empty_like(x)
+    if lib().rvcx_highpass_exact(x.ctypes.data_as(C.POINTER(C.c_double)), y.ctypes.data_as(C.POINTER(C.c_double)),
+                                 C.c_int64(x.shape[0])) != 0:
+        raise RvcxError("highpass_exact: " + (lib().rvcx_last_error(None) or b"").decode())
+    return y
 
 
 def _p(a: Optional[np.ndarray], ctype=C.c_float):
@@ -738,6 +750,18 @@ class Context:
         buf = (C.c_int32 * cap)()
         k = int(lib().rvcx_last_micro_batches(self._h, buf, cap))
         return [int(buf[i]) for i in range(min(k, cap))]
+
+    def last_cuts(self):
+        """the cut points (the reference's opt_ts) the last convert_batch call cut each clip at, in call order"""
+        k = int(lib().rvcx_last_cuts(self._h, None, 0))
+        buf = np.zeros(max(k, 1), np.int64)
+        lib().rvcx_last_cuts(self._h, buf.ctypes.data, k)
+        out, i = [], 0
+        while i < k:
+            c = int(buf[i])
+            out.append([int(v) for v in buf[i + 1:i + 1 + c]])
+            i += 1 + c
+        return out
 
     def get_f0_x(self, x, params: "Params"):
         """VC.get_f0 on the already padded + filtered signal: (coarse, f0) of 1 + n/160 frames."""

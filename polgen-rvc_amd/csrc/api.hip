@@ -1575,6 +1575,21 @@ int rvcx_last_micro_batches(rvcx_ctx* ctx, int32_t* counts, int cap) {
   return (int)v.size();
 }
 
+int64_t rvcx_last_cuts(rvcx_ctx* ctx, int64_t* out, int64_t cap) {
+  CtxLock ctx_guard_ = lock_ctx(ctx);
+  if (!ctx) return -1;
+  int64_t k = 0;
+  auto put = [&](int64_t v) {
+    if (out && k < cap) out[k] = v;
+    ++k;
+  };
+  for (const auto& cuts : ctx->c.last_cuts) {
+    put((int64_t)cuts.size());
+    for (long t : cuts) put(t);
+  }
+  return k;
+}
+
 int rvcx_get_f0(rvcx_ctx* ctx, const float* wav16k, int64_t n, const rvcx_params* p, int32_t* coarse, float* f0,
                 int64_t* p_len) {
   API_BEGIN(ctx)
@@ -1824,6 +1839,17 @@ int rvcx_op_highpass(rvcx_ctx* ctx, const double* x, double* y, int64_t n) {
   RVCX_HIP(hipStreamSynchronize(C->stream));
   C->arena.reset();
   API_END
+}
+
+int rvcx_highpass_exact(const double* x, double* y, int64_t n) {
+  try {
+    if (!x || !y) fail("highpass_exact: null pointer");
+    highpass_exact_host(x, n, y);
+    return 0;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return -1;
+  }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -221,6 +221,7 @@ struct Ctx {
   int launch_seq = 0;             // launches of split-fp16 kernels since the call began (orders the layers' overflow stamps)
   float timing[9] = {0};
   std::vector<int> last_mbs;      // member counts of the micro-batches of the last convert_batch call
+  std::vector<std::vector<long>> last_cuts;   // the cut points (opt_ts) each utterance of that call was cut at
   StageTimer timer;
   std::unique_ptr<HubertModel> hubert;
   std::unique_ptr<RmvpeModel> rmvpe;

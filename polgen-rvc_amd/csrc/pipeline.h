@@ -23,6 +23,12 @@ size_t highpass_ext_doubles(long n);   // scratch per signal the caller provides
 // ns[b] <= n samples -- it is filtered as a signal of exactly that length, the rest of its output row is zero
 void launch_highpass(const float* x32, const double* x64, double* ext, double* y64, float* y32, long n,
                      hipStream_t s, int B = 1, long xs = 0, const int* ns = nullptr);
+// scipy.signal.filtfilt(BH, AH, x) on the host, serial and bit for bit (n > 18; x and y may alias)
+void highpass_exact_host(const double* x, long n, double* y);
+// VC.pipeline's opt_ts (pipeline.py:329-344) of an n-sample clip (float32 input: its float64 values), from
+// highpass_exact_host's arithmetic: cut_count(n) values
+template <typename T>
+std::vector<long> exact_cut_points(const T* x, long n, const Geometry& g);
 
 // one utterance of a rvcx_convert_batch call.  wav / wav64 / noise / out / out_f32 may be host or device memory.
 struct UttIO {

@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <functional>
+#include <future>
 
 #include "models.h"
 #include "ops.h"
@@ -196,47 +197,105 @@ void launch_highpass(const float* x32, const double* x64, double* ext, double* y
 
 size_t highpass_ext_doubles(long n) { return 2 * ((size_t)n + 2 * PADLEN) + 16; }
 
-// ---------------------------------------------------------------- chunk search (pipeline.py:330-344)
-// audio_sum[i] = sum_{j<160} reflect_pad(audio,80)[i+j]  (same left-to-right order as the numpy loop)
-__global__ void window_abs_sum_kernel(const double* audio, double* asum, long n) {
-  for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    double acc = 0.0;
-    for (int j = 0; j < 160; ++j) {
-      long p = i + j - 80;
-      if (p < 0) p = -p;
-      if (p >= n) p = 2 * (n - 1) - p;
-      acc += audio[p];
-    }
-    asum[i] = fabs(acc);
+// ---------------------------------------------------------------- chunk search (pipeline.py:329-344)
+// The cut search cannot use the sliced filter above.  In a stretch of digital silence the high-passed signal is only the
+// filter's decaying tail, and the cut lands where that tail is smallest.  The sliced filter truncates the tail to exact
+// zeros about 3.3k samples into a gap (each slice forgets what lies before its warm-up), so the first-index minimum falls
+// on the first of them instead of where scipy's tail is smallest: up to a whole query window off.  Carrying the state
+// across slices does not help: the zero-input transition over a slice has condition number ~1e17 in DF2T coordinates.
+// So the search runs on scipy's own serial recursion, evaluated in scipy's operation order without contraction, which
+// reproduces scipy.signal.filtfilt bit for bit; the window sums then mirror numpy's loop and give the reference's opt_ts.
+
+// scipy.signal.lfilter_zi(BH, AH) as scipy 1.15.3 returns it (numpy.linalg.solve), repr() digits (they round-trip).
+// lfilter_zi() above solves the same system by its own elimination and may differ in the last bit.
+static const double ZI_SCIPY[5] = {-0.9699604796995847, 3.8798419288925783, -5.819762908173043, 3.879841948472456,
+                                   -0.9699604894923387};
+
+// scipy.signal.lfilter's direct-form II transposed loop (_linear_filter, RAWFILTER) over v in place, walking backwards
+// when rev, from the state ZI_SCIPY * x0 (default: the first sample it reads)
+static void lfilter_serial(double* v, long m, bool rev, double x0 = NAN) {
+#pragma clang fp contract(off)
+  if (std::isnan(x0)) x0 = v[rev ? m - 1 : 0];      // the backward pass of a partial range passes the signal's last sample
+  double z[5];
+  for (int k = 0; k < 5; ++k) z[k] = ZI_SCIPY[k] * x0;
+  for (long i = 0; i < m; ++i) {
+    double& e = v[rev ? m - 1 - i : i];
+    const double x = e;
+    const double y = z[0] + BH[0] * x;
+    z[0] = z[1] + x * BH[1] - y * AH[1];
+    z[1] = z[2] + x * BH[2] - y * AH[2];
+    z[2] = z[3] + x * BH[3] - y * AH[3];
+    z[3] = z[4] + x * BH[4] - y * AH[4];
+    z[4] = x * BH[5] - y * AH[5];
+    e = y;
   }
 }
 
-__global__ void argmin_first_kernel(const double* v, long lo, long hi, long* out) {
-  __shared__ double bv[256];
-  __shared__ long bi[256];
-  double best = INFINITY;
-  long idx = hi;
-  for (long i = lo + threadIdx.x; i < hi; i += 256)
-    if (v[i] < best) {
-      best = v[i];
-      idx = i;
-    }
-  bv[threadIdx.x] = best;
-  bi[threadIdx.x] = idx;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (threadIdx.x < o) {
-      const double ov = bv[threadIdx.x + o];
-      const long oi = bi[threadIdx.x + o];
-      if (ov < bv[threadIdx.x] || (ov == bv[threadIdx.x] && oi < bi[threadIdx.x])) {
-        bv[threadIdx.x] = ov;
-        bi[threadIdx.x] = oi;
-      }
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *out = bi[0];
+// filtfilt of x (double or float, taken as its float64 values) into e[PADLEN, PADLEN + n) of e (n + 2 PADLEN doubles).  The
+// backward pass runs from the end down to index `stop` of the output only: samples before it are left unfinished.
+template <typename T>
+static void filtfilt_into(const T* x, long n, double* e, long stop) {
+#pragma clang fp contract(off)
+  RVCX_CHECK(n > PADLEN, "highpass: input shorter than filtfilt's pad length");
+  const long m = n + 2 * PADLEN;
+  const double x0 = x[0], xn = x[n - 1];
+  for (long i = 0; i < PADLEN; ++i) e[i] = 2.0 * x0 - (double)x[PADLEN - i];          // scipy's odd_ext
+  for (long i = 0; i < n; ++i) e[PADLEN + i] = (double)x[i];
+  for (long j = 0; j < PADLEN; ++j) e[PADLEN + n + j] = 2.0 * xn - (double)x[n - 2 - j];
+  lfilter_serial(e, m, false);
+  const long from = std::max(0L, PADLEN + stop);
+  lfilter_serial(e + from, m - from, true, e[m - 1]);
 }
+
+void highpass_exact_host(const double* x, long n, double* y) {
+  std::unique_ptr<double[]> e(new double[(size_t)n + 2 * PADLEN]);
+  filtfilt_into(x, n, e.get(), 0);
+  for (long i = 0; i < n; ++i) y[i] = e[PADLEN + i];
+}
+
+template <typename T>
+std::vector<long> exact_cut_points(const T* x, long n, const Geometry& g) {
+  std::vector<long> cuts;
+  if (n + 160 <= g.t_max) return cuts;
+  // np.pad(audio, (80, 80), mode="reflect") in one buffer: the filter's odd extension fits inside the 80-sample pads
+  std::unique_ptr<double[]> buf(new double[(size_t)n + 160]);
+  double* ap = buf.get();
+  const long lo0 = std::max<long>(0, g.t_center - g.t_query);      // the first cut window's sums read from lo0 - 80 on
+  filtfilt_into(x, n, ap + 80 - PADLEN, std::max(0L, lo0 - 80));
+  for (long i = 0; i < 80; ++i) {
+    ap[79 - i] = ap[80 + std::min(i + 1, n - 1)];
+    ap[80 + n + i] = ap[80 + std::max(n - 2 - i, 0L)];
+  }
+  // every window on its own thread: the sums are independent, the order inside each stays numpy's
+  auto search = [&](long t) {
+    constexpr long BLK = 512;
+    double acc[BLK];
+    const long lo = std::max<long>(0, t - g.t_query), hi = std::min<long>(n, t + g.t_query);
+    double best = INFINITY;
+    long arg = lo;
+    for (long b0 = lo; b0 < hi; b0 += BLK) {
+      const long nb = std::min(BLK, hi - b0);
+      // audio_sum[i] = ((0 + pad[i]) + pad[i+1]) + ... + pad[i+159]: numpy's `audio_sum += audio_pad[i:i-160]` order
+      for (long k = 0; k < nb; ++k) acc[k] = 0.0;
+      for (long j = 0; j < 160; ++j) {
+        const double* p = ap + b0 + j;
+        for (long k = 0; k < nb; ++k) acc[k] += p[k];
+      }
+      for (long k = 0; k < nb; ++k)
+        if (std::fabs(acc[k]) < best) {       // strict: the first index of the minimum (np.where(...)[0][0])
+          best = std::fabs(acc[k]);
+          arg = b0 + k;
+        }
+    }
+    return arg;
+  };
+  std::vector<std::future<long>> win;
+  for (long t = g.t_center; t < n; t += g.t_center) win.push_back(std::async(std::launch::async, search, t));
+  for (auto& w : win) cuts.push_back(w.get());
+  return cuts;
+}
+template std::vector<long> exact_cut_points<double>(const double*, long, const Geometry&);
+template std::vector<long> exact_cut_points<float>(const float*, long, const Geometry&);
 
 // ---------------------------------------------------------------- post-processing
 // librosa.feature.rms(frame_length=sr, hop=sr/2, center=True zero pad) -> n_frames values (f32)
@@ -408,6 +467,7 @@ struct Utt {
   const int* coarse = nullptr;
   const float* f0 = nullptr;
   std::vector<Chunk> plan;
+  std::future<std::vector<long>> cuts;   // the cut search of a clip longer than x_max (host thread, exact_cut_points)
 };
 
 struct Job {                  // one vc() call of the reference: chunk `ci` of utterance `u` (index in the micro-batch)
@@ -596,10 +656,10 @@ long get_f0_device(Ctx& c, const float* apad, long n_pad, const rvcx_params& p, 
 // Utterances of equal length form micro-batches that go through every network as one launch sequence with B > 1
 // (chunks of cut utterances are batch items too when their lengths agree): the serial BiGRU recurrence, the ~600
 // small launches of the front end and the TextEncoder/flow section are paid once per micro-batch instead of once
-// per clip.  Three streams: `sf` runs the front end (upload, float64 zero-phase high-pass, cut search, reflect
+// per clip.  Three streams: `sf` runs the front end (upload, float64 zero-phase high-pass, reflect
 // pad, RMVPE F0) of micro-batch k+1 while the main stream is still in the NSF decoder of micro-batch k; HuBERT keeps
-// its CU-masked stream; finished PCM leaves behind its micro-batch on the main stream.  No host synchronisation inside the loop except
-// the cut-point read-back of clips longer than x_max seconds.
+// its CU-masked stream; finished PCM leaves behind its micro-batch on the main stream.  No host synchronisation inside the
+// loop; the cut search of clips longer than x_max seconds runs on host threads and is joined before HuBERT is enqueued.
 void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_params& p, float* stage_ms) {
   RVCX_CHECK(c.hubert != nullptr, "convert: hubert not loaded");
   check_f0_backend(c, p);
@@ -652,6 +712,7 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   }
   c.last_mbs.clear();
   for (const auto& mb : mbs) c.last_mbs.push_back(mb.count);
+  c.last_cuts.assign(NB, {});
   size_t call_bytes = 0, mb_bytes = 0, f0_bytes = 0, hub_bytes = 0;
   for (const auto& u : ios) {
     any_f64 |= u.wav64 != nullptr;
@@ -716,7 +777,6 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     double *ext = nullptr, *a64 = nullptr, *asum = nullptr;
     float *a32 = nullptr, *apad = nullptr, *f0 = nullptr;
     int* coarse = nullptr;
-    long* cuts = nullptr;
     float* feats = nullptr;     // HuBERT features of every chunk of the micro-batch, group after group
     size_t feats_cap = 0;
     int* ns = nullptr;          // device: the members' sample counts (ragged micro-batches)
@@ -724,7 +784,7 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   size_t front_items = 0;
   for (const auto& mb : mbs) front_items = std::max(front_items, (size_t)mb.count);
   {
-    size_t wmax = 0, emax = 0, nmax = 0, pmax = 0, fmax = 0, cmax = 0, hmax = 0;
+    size_t wmax = 0, emax = 0, nmax = 0, pmax = 0, fmax = 0, hmax = 0;
     for (const auto& mb : mbs) {
       const long n = mb.nd;
       const size_t k = (size_t)mb.count;
@@ -733,19 +793,17 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       nmax = std::max(nmax, k * (size_t)n);
       pmax = std::max(pmax, k * (size_t)(n + 2 * g.t_pad));
       fmax = std::max(fmax, k * (size_t)((n + 2 * g.t_pad) / 160 + 8));
-      cmax = std::max(cmax, k * (size_t)(cut_count(n, g) + 1));
       // every chunk carries 2 * t_pad samples of context beyond its share of the clip
       hmax = std::max(hmax, k * (size_t)E * (size_t)((n + 2 * g.t_pad + (cut_count(n, g) + 1) * (2 * g.t_pad + 640)) / 320 + 8));
     }
     for (auto& f : fr) {
       f.wav = A.alloc<char>(wmax);
-      f.ext = A.alloc<double>(emax);    // also the |window sum| scratch of the cut search (same size class)
+      f.ext = A.alloc<double>(emax);
       f.a64 = A.alloc<double>(nmax);
       f.a32 = A.alloc<float>(nmax);
       f.apad = A.alloc<float>(pmax);
       f.f0 = A.alloc<float>(fmax);
       f.coarse = A.alloc<int>(fmax);
-      f.cuts = A.alloc<long>(cmax);
       f.feats = A.alloc<float>(hmax);
       f.feats_cap = hmax;
       f.ns = A.alloc<int>(front_items);
@@ -769,8 +827,8 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   // Measured on C3 (64 x 30 s): 1036 / 1030 / 1031 x -- at B = 8 HuBERT and the F0 model are throughput-bound like the
   // decoder, so WHERE they overlap the main stream does not matter: the sum of the kernel times is what it is.
   static const int front_delay = getenv("RVCX_FRONT_DELAY") ? atoi(getenv("RVCX_FRONT_DELAY")) : 0;
-  // ---- front end of one micro-batch on `sf`: upload, high-pass, cut search, reflect pad.  Returns after the
-  // (rare) cut-point read-back, so the chunk plan is known to the host.
+  // ---- front end of one micro-batch on `sf`: upload, high-pass, reflect pad.  The cut search of clips longer than x_max
+  // starts on host threads (exact_cut_points) and runs beside the F0 model; finish_front(k) collects it into the chunk plans.
   auto front = [&](int k) {
     const MB& mb = mbs[k];
     Front& f = fr[k & 1];
@@ -797,28 +855,33 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     }
     launch_highpass(f64 ? nullptr : static_cast<const float*>(f.wav), f64 ? static_cast<const double*>(f.wav) : nullptr,
                     f.ext, f.a64, f.a32, n, sf, Bm, n, d_ns);
-    // chunk cut points (pipeline.py:330-344): only clips longer than t_max are cut
+    // chunk cut points (pipeline.py:329-344): only clips longer than t_max are cut
     const long ncut = cut_count(ios[order[mb.first]].n, g);     // cut clips are never ragged: n is their own length
     RVCX_CHECK(ncut == 0 || !mb.ragged, "internal: a cut clip in a ragged micro-batch");
-    std::vector<long> cuts((size_t)Bm * ncut);
     if (ncut > 0) {
       for (int b = 0; b < Bm; ++b) {
-        double* asum = f.ext + (size_t)b * highpass_ext_doubles(n);   // the filter scratch is free again
-        hipLaunchKernelGGL(window_abs_sum_kernel, dim3((unsigned)std::min<long>(cdiv64(n, 256), 65535)), dim3(256), 0,
-                           sf, f.a64 + (size_t)b * n, asum, n);
-        long i = 0;
-        for (long t = g.t_center; t < n; t += g.t_center, ++i) {
-          const long lo = std::max<long>(0, t - g.t_query), hi = std::min<long>(n, t + g.t_query);
-          hipLaunchKernelGGL(argmin_first_kernel, dim3(1), dim3(256), 0, sf, asum, lo, hi, f.cuts + (size_t)b * ncut + i);
+        const UttIO& io = ios[order[mb.first + b]];
+        const void* src = f64 ? static_cast<const void*>(io.wav64) : static_cast<const void*>(io.wav);
+        const size_t bytes = (size_t)io.n * (f64 ? 8 : 4);
+        std::vector<char> copy;
+        hipPointerAttribute_t pa;
+        if (hipPointerGetAttributes(&pa, src) == hipSuccess && pa.type == hipMemoryTypeDevice) {
+          copy.resize(bytes);                        // device input (rare): the serial filter reads a host copy
+          RVCX_HIP(hipMemcpy(copy.data(), src, bytes, hipMemcpyDeviceToHost));
+          src = copy.data();
+        } else {
+          (void)hipGetLastError();                   // plain host memory is not known to HIP
         }
-        RVCX_CHECK(i == ncut, "internal: cut count");
+        // float32 input is filtered as the float64 of its values, like launch_highpass does
+        utts[order[mb.first + b]].cuts = std::async(std::launch::async, [src, f64, n, g, copy = std::move(copy)]() {
+          return f64 ? exact_cut_points(static_cast<const double*>(src), n, g)
+                     : exact_cut_points(static_cast<const float*>(src), n, g);
+        });
       }
-      RVCX_HIP(hipMemcpyAsync(cuts.data(), f.cuts, cuts.size() * sizeof(long), hipMemcpyDeviceToHost, sf));
     }
     launch_reflect_pad(f.a32, f.apad, Bm, (int)n, (int)g.t_pad, n_pad, sf, d_ns);   // zeros behind a shorter member
     if (sf != s) RVCX_HIP(hipEventRecord(c.ev_front[k & 1], sf));
     spans.push_back({h0, clk.mark(sf), &t_hp});
-    if (ncut > 0) RVCX_HIP(hipStreamSynchronize(sf));
     const long stride = n_pad / 160 + 8;
     for (int b = 0; b < Bm; ++b) {
       Utt& u = utts[order[mb.first + b]];
@@ -826,8 +889,17 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       u.apad = f.apad + (size_t)b * n_pad;
       u.coarse = f.coarse + (size_t)b * stride;
       u.f0 = f.f0 + (size_t)b * stride;
-      std::vector<long> opt(cuts.begin() + (size_t)b * ncut, cuts.begin() + (size_t)(b + 1) * ncut);
+    }
+  };
+  // the chunk plans of micro-batch k, once its cut search is done (HuBERT, the first user of the plan, is enqueued behind it)
+  auto finish_front = [&](int k) {
+    const MB& mb = mbs[k];
+    for (int b = 0; b < mb.count; ++b) {
+      Utt& u = utts[order[mb.first + b]];
+      std::vector<long> opt;
+      if (u.cuts.valid()) opt = u.cuts.get();
       u.plan = plan_chunks(u.n, opt, g);
+      c.last_cuts[u.io] = std::move(opt);
     }
   };
 
@@ -1024,8 +1096,11 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   static const int hub_gate_env = getenv("RVCX_HUBERT_GATE") ? atoi(getenv("RVCX_HUBERT_GATE")) : -1;
   auto enqueue_models = [&](int k) {
     bool hub_done = false, from_hook = true;
+    bool cutting = false;
+    for (int b = 0; b < mbs[k].count; ++b) cutting |= utts[order[mbs[k].first + b]].cuts.valid();
     const std::function<void()> mid = [&]() {
-      if (hub_done) return;
+      // a cut search still running on the host: the F0 recurrence goes first, HuBERT (which needs the plan) behind it
+      if (hub_done || (cutting && from_hook)) return;
       hub_done = true;
       if (k == 0) mid_mark = clk.mark(sf);
       const bool hub_gate = hub_gate_env < 0 ? (mbs[k].count <= 1 || (k == 0 && mbs[k].count < 8)) : hub_gate_env != 0;
@@ -1033,6 +1108,8 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
         RVCX_HIP(hipEventRecord(c.ev_hub, sf));
         RVCX_HIP(hipStreamWaitEvent(sh, c.ev_hub, 0));
       }
+      finish_front(k);
+      plan_jobs(k);
       enqueue_hubert(k);
     };
     enqueue_f0(k, &mid);
@@ -1047,7 +1124,6 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       fprintf(stderr, "[host] mb %d %-14s %9.3f ms\n", k, what,
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ht0).count());
   };
-  plan_jobs(0);
   enqueue_models(0);
   ht("hubert+f0", 0);
   for (int k = 0; k < (int)mbs.size(); ++k) {
@@ -1227,7 +1303,6 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     if (k + 1 < (int)mbs.size()) {
       front(k + 1);
       ht("front", k + 1);
-      plan_jobs(k + 1);
       enqueue_models(k + 1);
       ht("hubert+f0", k + 1);
     }

@@ -554,6 +554,15 @@ def make_clip(index: int, seconds: float, sr: int = 16000) -> np.ndarray:
     return x.astype(np.float32)
 
 
+def make_gapped_clip(index: int, seconds: float, zero_spans=(), sr: int = 16000) -> np.ndarray:
+    """make_clip(index, seconds) with digital silence: every (start, end) span in seconds set to exact zeros.  index < 0:
+    a clip of zeros only.  The recipe of the silence fixtures (tools/gen_golden.py)."""
+    x = np.zeros(int(round(seconds * sr)), np.float32) if index < 0 else make_clip(index, seconds, sr)
+    for a, b in zero_spans:
+        x[int(round(a * sr)):int(round(b * sr))] = 0.0
+    return x
+
+
 def make_index(n: int, dim: int = 768, seed: int = 0) -> np.ndarray:
     """Synthetic retrieval matrix (the ``big_npy`` of pipeline.py:323)."""
     return _normal(f"index.{n}.{dim}", (n, dim), 1.0, seed)

@@ -69,6 +69,17 @@ def test_highpass_matches_scipy(ctx):
     assert np.abs(got - ref).max() < 1e-6
 
 
+def test_highpass_matches_scipy_gapped(ctx):
+    """The same bar on a clip with digital silence: zero ends and a 1.2 s zero gap, where the output is only the filter's
+    decaying tail (the sliced recursion truncates it to exact zeros; absolute error stays tiny)."""
+    from oracle import pipeline as OP
+    from polgen_rvc_amd import synthetic as S
+    x = S.make_gapped_clip(5, 3.0, [(0.0, 0.3), (1.1, 2.3), (2.8, 3.0)]).astype(np.float64)
+    ref = OP.highpass(x)
+    got = ctx.highpass(x)
+    assert np.abs(got - ref).max() < 1e-6
+
+
 @pytest.mark.parametrize("tag", ["tiny_single", "tiny_ciargs", "tiny_chunked", "tiny_short", "tiny_sid3_noprotect"])
 def test_pipeline_vs_reference_golden(ctx, tag):
     from polgen_rvc_amd import synthetic as S

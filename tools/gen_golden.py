@@ -49,6 +49,7 @@ class _FlatIndex:
         self.big = np.ascontiguousarray(big, np.float32)
         self.ntotal, self.d = self.big.shape
         self.searches = []
+        self.dists = []
 
     def reconstruct_n(self, i0, n):
         return self.big[i0:i0 + n]
@@ -58,6 +59,7 @@ class _FlatIndex:
         d2 = (q * q).sum(1)[:, None] - 2.0 * q @ b.T + (b * b).sum(1)[None, :]
         ix = np.argsort(d2, axis=1, kind="stable")[:, :k]
         self.searches.append(ix.copy())
+        self.dists.append(np.sort(d2, axis=1)[:, :9])
         return np.take_along_axis(d2, ix, axis=1).astype(np.float32), ix.astype(np.int64)
 
 
@@ -304,6 +306,9 @@ def gold_hubert(tag, cfg, seconds, seed, outliers=False):
                         out_l1=out.hidden_states[1].numpy(), **extra)
 
 
+VC_IN_LENS = []
+
+
 def run_ref_pipeline(models_cfg, geo, audio, pitch, volume_envelope, protect, f0_min, f0_max, seed,
                      tgt_sr, file_index=None, index_rate=0, prebuilt=None, f0_method="rmvpe+", version="v2", sid=0):
     (hcfg, hsd), (rcfg, rsd), (scfg, ssd) = models_cfg
@@ -329,8 +334,10 @@ def run_ref_pipeline(models_cfg, geo, audio, pitch, volume_envelope, protect, f0
     def vc_cap(*a, **kw):
         r = orig_vc(*a, **kw)
         raw.append(r.copy())
+        VC_IN_LENS.append(len(a[3]))          # the audio_pad slice this vc() call got
         return r
     vc.vc = vc_cap
+    VC_IN_LENS.clear()
     torch.randn_like = cap
     torch.manual_seed(seed)
     try:
@@ -390,6 +397,137 @@ def gold_pipeline(tag, cfgs, geo, seconds, clip, seed, pitch, volume_envelope, p
     else:
         store.update(pcm_samples=pcm[::997], raw_samples=rawcat[::997].astype(np.float32), noise_seed=seed)
     np.savez_compressed(os.path.join(GOLD, f"pipeline_{tag}.npz"), **store)
+
+# ------------------------------------------------------------------ digital silence
+def silence_recipe_cuts(clip, seconds, zero_spans, geo):
+    """The recipe's input, scipy's filtfilt of it, the reference's opt_ts on that (oracle.chunk_points restates
+    pipeline.py:329-344) and the conditioning of every cut window (oracle.pipeline.cut_margins)."""
+    audio = S.make_gapped_clip(clip, seconds, zero_spans)
+    filt = O_pipe.highpass(audio.astype(np.float64))
+    g = O_pipe.Geometry(48000, *geo)
+    return audio, filt, [int(t) for t in O_pipe.chunk_points(filt, g)], O_pipe.cut_margins(filt, g)
+
+
+def gold_pipeline_silence(tag, clip, seconds, zero_spans, geo, volume_envelope, seed=1, silent=False, stride=1,
+                          index_centers=0, index_rate=0.75):
+    """VC.pipeline on a clip with digital silence (make_gapped_clip: a make_clip index, or -1 for zeros, and the zeroed
+    spans), tiny models.  Stores the recipe, the reference's cut points and what gold_pipeline stores.  stride > 1 (long
+    clips, 1 MiB per file): the Gaussian draws are left to be regenerated from the private generator's seed, and the float
+    waveform is kept at every stride-th sample (block_rms still covers every sample).  index_centers > 0: a retrieval index
+    of that many random centres in 8 identical copies each (the top 8 of a query are the copies of its nearest centre, so
+    the ids are unambiguous when the nearest centre is: asserted at >= 1e-3 relative distance gap for every query of every
+    chunk; one centre lies near the features, the others far out), searched at index_rate -- with the protect mix (0.33) this makes feats0 != feats on unvoiced frames."""
+    hcfg, rcfg, scfg = S.HUBERT_CFG_TINY, S.RMVPE_CFG_TINY, S.SYNTH_CFG_TINY
+    print(f"[pipeline {tag}] clip {clip} {seconds}s zeros {zero_spans} geo={geo} env={volume_envelope}")
+    audio, filt, cuts, margins = silence_recipe_cuts(clip, seconds, zero_spans, geo)
+    # Condition on the input, not a tolerance: every cut window is all exact zeros (every index ties, the first wins), or
+    # every index of another frame than the chosen one has |audio_sum| >= 1.01 x the minimum -- a filter that is off by
+    # rounding (~1e-8 relative) cannot move the cut to another frame.  A failing window means: move the gap.
+    print(f"  cuts {cuts}, window margins {margins}")
+    assert all(m is None or m >= 1.01 for m in margins), (tag, margins)
+    if silent:
+        assert not filt.any() and all(m is None for m in margins), tag
+    a_ = np.pad(filt, (16000 * geo[0], 16000 * geo[0]), mode="reflect").astype(np.float32)
+    if silent:
+        # the RMVPE seed must leave digital silence unvoiced (f0 == 0 on every frame) and well-conditioned
+        for k in range(40):
+            sd_ = S.to_torch(S.rmvpe_state(rcfg, seed + 100 * k))
+            f0_, hid_, _ = O_rmvpe.infer_f0(sd_, rcfg, a_, 0.03, 50, 1100, return_hidden=True)
+            if not (f0_ > 0).any() and len(O_rmvpe.unstable_frames(hid_, 0.03, 50, 1100)) == 0:
+                seed += 100 * k
+                break
+        else:
+            raise RuntimeError("no seed leaves silence unvoiced")
+    else:
+        seed = stable_seed(rcfg, a_, seed)
+    hsd, rsd, ssd = (S.to_torch(S.hubert_state(hcfg, seed)), S.to_torch(S.rmvpe_state(rcfg, seed)),
+                     S.to_torch(S.synth_state(scfg, seed, input_dim=hcfg["embed_dim"])))
+    tgt_sr = scfg[-1]
+    big, path, irate = None, None, 0.0
+    for iseed in range(20 if index_centers else 1):
+        if index_centers:
+            cen = S.make_index(index_centers, hcfg["embed_dim"], iseed)
+            cen[0] *= 0.1                         # one centre near the features, the others 10x farther out
+            cen[1:] *= 10.0
+            big = np.repeat(cen, 8, axis=0)
+            idx = _FlatIndex(big)
+            path = os.path.join("/tmp", f"rvcx_{tag}.index")
+            open(path, "wb").close()
+            _INDEX_FILES[path] = idx
+            irate = index_rate
+        pcm, raw, noises = run_ref_pipeline(((hcfg, hsd), (rcfg, rsd), (scfg, ssd)), geo, audio, 0, volume_envelope, 0.33,
+                                            50, 1100, seed, tgt_sr, file_index=path, index_rate=irate)
+        if not index_centers:
+            break
+        os.remove(path)
+        assert len(idx.searches) == len(raw), "the reference did not search the index"
+        gap = min(float(np.min((d[:, 8] - d[:, 7]) / d[:, 7])) for d in idx.dists)
+        print(f"  index seed {iseed}: smallest relative gap nearest / next centre {gap:.2e}")
+        if gap >= 1e-3:
+            break
+    else:
+        raise RuntimeError("no index seed with unambiguous neighbours")
+    # the reference's cuts from its own vc() calls: chunk i < last gets audio_pad[s : t + 2 t_pad + 160] with
+    # t = opt_ts[i] // 160 * 160 and s the previous t (pipeline.py:381-415)
+    t_pad = 16000 * geo[0]
+    s_, got = 0, []
+    for ln in VC_IN_LENS[:-1]:
+        s_ = s_ + ln - 2 * t_pad - 160
+        got.append(s_)
+    assert len(raw) == len(cuts) + 1 and got == [c // 160 * 160 for c in cuts], (tag, got, cuts)
+    assert VC_IN_LENS[-1] == len(audio) + 2 * t_pad - (got[-1] if got else 0), tag
+    models = O_pipe.Models(hsd, hcfg, rsd, rcfg, ssd, scfg)
+    opcm, parts = O_pipe.pipeline(models, O_pipe.Geometry(tgt_sr, *geo), audio, 0, 0, big, irate, volume_envelope, 0.33,
+                                  50, 1100, noises=noises, return_parts=True)
+    e = 0.0
+    for i, (a, b) in enumerate(zip(raw, parts["raw"])):
+        e = max(e, report(f"vc chunk {i} f32", a, b))
+    d = np.abs(pcm.astype(np.int32) - opcm.astype(np.int32))
+    print(f"  chunks={len(raw)} pcm: max |diff| = {d.max()} LSB; voiced frames {int((parts['f0'] > 0).sum())}/"
+          f"{len(parts['f0'])}; pcm peak {np.abs(pcm).max()}")
+    assert e < 1e-4 and d.max() <= 8, (e, d.max())
+    rawcat = np.concatenate(raw)
+    store = dict(seed=seed, clip=clip, seconds=seconds, zero_spans=np.array(zero_spans, np.float64).reshape(-1, 2),
+                 cuts=np.array(cuts, np.int64), geo=np.array(geo), pitch=0.0, version="v2", sid=0,
+                 volume_envelope=volume_envelope, protect=0.33, f0_min=50, f0_max=1100,
+                 cfgs=json.dumps([hcfg, rcfg, scfg]), n_chunks=len(raw), chunk_lens=np.array([len(r) for r in raw]),
+                 f0=parts["f0"].astype(np.float32), coarse=parts["coarse"].astype(np.int16),
+                 sha256=hashlib.sha256(pcm.tobytes()).hexdigest(),
+                 block_rms=np.array([rms(rawcat[i:i + 4096]) for i in range(0, len(rawcat), 4096)], np.float32),
+                 pcm=pcm, stride=stride, noise_seed=seed)
+    if index_centers:
+        store.update(index_rows=big.astype(np.float32), index_rate=irate, index_seed=iseed)
+    if stride == 1:
+        store["raw"] = rawcat.astype(np.float32)
+        for i, (zn, sn) in enumerate(noises):
+            store[f"z_noise_{i}"] = zn.numpy()
+            store[f"src_noise_{i}"] = sn.numpy()
+    else:
+        store["raw_samples"] = rawcat[::stride].astype(np.float32)
+        gen = torch.Generator().manual_seed(int(seed))       # what tests/test_gpu_silence.py regenerates
+        for zn, sn in noises:
+            assert torch.equal(torch.randn(zn.shape, generator=gen), zn) and torch.equal(torch.randn(sn.shape, generator=gen), sn)
+    np.savez_compressed(os.path.join(GOLD, f"pipeline_{tag}.npz"), **store)
+
+
+# tag -> recipe (make_gapped_clip's clip index, -1 = zeros, and zeroed spans in seconds) and settings.  The gaps sit under
+# every cut window; tests/test_silence_recipes.py re-derives the cuts and the window check from these recipes.
+SILENCE_RECIPES = {
+    "tiny_silent": dict(clip=-1, seconds=3.0, zero_spans=[], geo=(1, 6, 38, 41), volume_envelope=1.0, silent=True),
+    "tiny_silent_env": dict(clip=-1, seconds=3.0, zero_spans=[], geo=(1, 6, 38, 41), volume_envelope=0.25, silent=True),
+    "tiny_silent_cut": dict(clip=-1, seconds=7.0, zero_spans=[], geo=(1, 1, 2, 3), volume_envelope=1.0, silent=True),
+    "tiny_gap_cut": dict(clip=41, seconds=7.0, zero_spans=[(1.5, 2.5), (3.6, 4.8), (5.4, 6.2)], geo=(1, 1, 2, 3),
+                         volume_envelope=1.0),
+    # the same clip with the protect mix live: a retrieval index at index_rate 0.75 makes feats0 != feats, and the gaps'
+    # unvoiced frames take the blend (pipeline.py:252-262)
+    "tiny_gap_cut_index": dict(clip=41, seconds=7.0, zero_spans=[(1.5, 2.5), (3.6, 4.8), (5.4, 6.2)], geo=(1, 1, 2, 3),
+                               volume_envelope=1.0, index_centers=4),
+    "tiny_lead_trail": dict(clip=44, seconds=3.6, zero_spans=[(0.0, 0.6), (3.0, 3.6)], geo=(1, 1, 2, 3),
+                            volume_envelope=0.25),
+    "gap_real_geo": dict(clip=47, seconds=45.0, zero_spans=[(36.0, 37.5)], geo=(1, 6, 38, 41), volume_envelope=1.0,
+                         stride=3),
+}
+
 
 # ------------------------------------------------------------------ FCPE
 def fcpe_file(cfg, seed):
@@ -643,6 +781,8 @@ def main():
         # round 6: a speaker id other than 0 (row 3 of emb_g) and the protect mix switched off (protect >= 0.5, pipeline.py:252-262)
         "pipe_tiny_sid": lambda: gold_pipeline("tiny_sid3_noprotect", tiny, (1, 6, 38, 41), 2.1, 17, 1, 1.5, 0.6, 0.5, 50, 1100, sid=3),
         "pipe_tiny_v1": lambda: gold_pipeline("tiny_v1", tiny, (1, 6, 38, 41), 2.2, 16, 1, 0, 1.0, 0.33, 50, 1100, version="v1"),
+        # digital silence (SILENCE_RECIPES): zero clips, zero gaps under the cut windows, zero ends
+        **{f"pipe_{tag}": (lambda tag=tag: gold_pipeline_silence(tag, **SILENCE_RECIPES[tag])) for tag in SILENCE_RECIPES},
     }
     if a.full:
         full40 = (S.HUBERT_CFG_BASE, S.RMVPE_CFG_FULL, S.SYNTH_CFG_40K)

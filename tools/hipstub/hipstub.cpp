@@ -92,6 +92,11 @@ hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) {
   if (n) memmove(d, s, n);
   return hipSuccess;
 }
+hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void*) {
+  memset(a, 0, sizeof(*a));
+  a->type = hipMemoryTypeHost;    // every "device" allocation of the stub is host memory
+  return hipSuccess;
+}
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) {
   if (n) memmove(d, s, n);
   return hipSuccess;
