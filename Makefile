@@ -43,7 +43,29 @@ build/asan/librvcx_asan.so: $(ASAN_OBJS) build/asan/hipstub.o build/asan/fatbins
 
 host-asan: build/asan/librvcx_asan.so
 
+# ---- the same host pass under ThreadSanitizer (tools/host_tsan.sh runs tools/host_tickets_driver.py on it): conversion
+# tickets are the first code of the library where the state of two requests can meet
+TSAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -Wno-pass-failed -Wno-unused-result -fsanitize=thread \
+              -fno-omit-frame-pointer
+TSAN_OBJS := $(patsubst $(CSRC)/%.hip,build/tsan/%.o,$(SRCS))
+
+build/tsan/%.o: $(CSRC)/%.hip $(HDRS)
+	@mkdir -p build/tsan
+	$(HIPCC) $(TSAN_FLAGS) -c $< -o $@
+
+build/tsan/hipstub.o: tools/hipstub/hipstub.cpp
+	@mkdir -p build/tsan
+	$(HIPCC) $(TSAN_FLAGS) -x hip -c $< -o $@
+
+build/tsan/fatbins.c: $(TSAN_OBJS)
+	nm $(TSAN_OBJS) | awk '/ U __hip_fatbin_/ {print "char " $$2 "[64] = {0};"}' | sort -u > $@
+
+build/tsan/librvcx_tsan.so: $(TSAN_OBJS) build/tsan/hipstub.o build/tsan/fatbins.c
+	$(CLANGXX) -shared -fPIC -fsanitize=thread -shared-libsan $(TSAN_OBJS) build/tsan/hipstub.o build/tsan/fatbins.c -o $@
+
+host-tsan: build/tsan/librvcx_tsan.so
+
 clean:
 	rm -rf build $(OUT)
 
-.PHONY: all clean host-asan
+.PHONY: all clean host-asan host-tsan

@@ -234,6 +234,53 @@ int rvcx_convert_batch_f64(rvcx_ctx*, int model_id, int B, const double* const* 
 int rvcx_convert_batch_ex(rvcx_ctx*, int model_id, int B, const void* const* wav16k_hd, int wav_is_f64,
                           const int64_t* n, const rvcx_params* p, const float* const* noise_hd,
                           const rvcx_utt_extra* extra, int16_t* const* out_hd, float* const* out_f32_hd, int64_t* out_n);
+
+/* ---- conversion tickets: two requests in flight per context ----------------------------------------------------------
+ * rvcx_convert_submit takes the arguments of rvcx_convert_batch_ex, enqueues the conversion on the calling thread and
+ * returns a ticket without waiting for the device; rvcx_convert_wait blocks until the ticket's outputs and out_n are
+ * final.  What a ticket writes is byte for byte what rvcx_convert_batch_ex writes for the same arguments (utterance i of a
+ * ticket draws from Philox(seed + i)).  While one ticket is in its synthesizer on the main stream, the front end (upload,
+ * high-pass, F0 model, HuBERT) of the next one runs on the front / HuBERT streams, as consecutive micro-batches of one
+ * call do; tickets of different voice models or parameters take the same path.
+ *
+ * Borrowing.  submit copies n, *p, the pointer tables, `extra` and the f0-file rows it points to.  The audio, noise,
+ * crepe-dither and output buffers (and out_n) are BORROWED until rvcx_convert_wait has returned for the ticket: they must
+ * stay valid and untouched until then.  Outputs in plain host memory are written during the wait (or whenever the ticket
+ * is completed internally, see below), outputs in device or pinned memory by the device.
+ *
+ * Two in flight.  At most two tickets are in flight per context.  A third submit first completes the oldest one (that
+ * ticket stays waitable, its results are in the caller's buffers) and then proceeds.
+ *
+ * Order and threads.  Tickets may be waited for in any order and from any thread; completions are processed in submit
+ * order (waiting for the younger ticket settles the older one first).  wait does not hold the context's mutex while it
+ * blocks on the device.  Waiting twice for a ticket, or for a ticket of another context, returns -1 with a message.
+ *
+ * Other entry points.  Every other entry point of the context (synchronous conversions, F0 / HuBERT calls, loading or
+ * unloading a model or index, rvcx_destroy) first completes the tickets in flight; so does a submit that needs more of
+ * the memory consecutive tickets share than the context holds.  Completed tickets stay waitable.  The exception is
+ * rvcx_resample_f64 / rvcx_resample_f64_kind (what a caller decodes the NEXT request with): it runs beside the tickets
+ * in flight, in memory of its own.
+ *
+ * Range guard, BiGRU fallback.  The observable outcome equals that of the same requests issued as synchronous calls in
+ * submit order (rvcx_fp32_pinned and rvcx_gru_fallbacks included): each ticket has its own device error word; a ticket
+ * that met an activation beyond fp16 range is repeated as a synchronous call, and so is every ticket enqueued behind it
+ * before the layer was pinned; a BiGRU cluster time-out repeats that ticket alone.
+ *
+ * After rvcx_convert_wait(t), rvcx_last_micro_batches, rvcx_last_cuts and rvcx_last_timing describe ticket t. */
+typedef int64_t rvcx_ticket; /* > 0; never reused within a context */
+int rvcx_convert_submit(rvcx_ctx*, int model_id, int B, const void* const* wav16k_hd, int wav_is_f64,
+                        const int64_t* n, const rvcx_params* p, const float* const* noise_hd,
+                        const rvcx_utt_extra* extra, int16_t* const* out_hd, float* const* out_f32_hd,
+                        int64_t* out_n, rvcx_ticket* ticket);
+int rvcx_convert_wait(rvcx_ctx*, rvcx_ticket); /* blocks; 0 = the outputs and out_n are final */
+int rvcx_convert_poll(rvcx_ctx*, rvcx_ticket); /* 1 done (wait will not block on the device), 0 in flight, < 0 error */
+int rvcx_convert_inflight(rvcx_ctx*);          /* tickets submitted and not yet completed on the device */
+/* Valid after the wait: device time (HIP events) from the first front-end work of the ticket to the completion of the
+ * ticket submitted before it.  Positive: its front end started that many ms before its predecessor finished; 0 for a
+ * ticket submitted into an idle context.  The context remembers the figure of the last 256 tickets waited for; for
+ * any other ticket (older, never waited for, unknown, of another context) the result is NaN. */
+float rvcx_ticket_lead_ms(rvcx_ctx*, rvcx_ticket);
+
 /* utterances of n samples converted per launch sequence (memory-bounded; RVCX_MAX_BATCH, RVCX_ARENA_GB) */
 int rvcx_micro_batch(rvcx_ctx*, int model_id, int64_t n, const rvcx_params* p);
 /* The sample count whose launch geometry an n-sample utterance is converted with (>= n): utterances with equal values

@@ -8,6 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import threading
+import types
 from typing import Optional, Sequence
 
 import numpy as np
@@ -85,6 +86,7 @@ SYMBOLS = [
     "rvcx_op_bigru", "rvcx_op_highpass", "rvcx_highpass_exact", "rvcx_convert_batch_ex", "rvcx_get_f0_x_ex", "rvcx_fp32_layers", "rvcx_fp32_pinned",
     "rvcx_gru_fallbacks", "rvcx_gru_publish_probe", "rvcx_debug_inject", "rvcx_f0_file_track", "rvcx_op_gemm_tm", "rvcx_op_layernorm_tm",
     "rvcx_resample_len", "rvcx_resample_f64", "rvcx_resample_f64_kind", "rvcx_bench_gemm", "rvcx_device_info",
+    "rvcx_convert_submit", "rvcx_convert_wait", "rvcx_convert_poll", "rvcx_convert_inflight", "rvcx_ticket_lead_ms",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
 ]
 
@@ -121,6 +123,14 @@ def lib() -> C.CDLL:
         _lib.rvcx_flac_info.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _lib.rvcx_flac_decode_s32.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+        _lib.rvcx_convert_submit.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.POINTER(C.c_int64)]
+        _lib.rvcx_convert_wait.argtypes = [C.c_void_p, C.c_int64]
+        _lib.rvcx_convert_poll.argtypes = [C.c_void_p, C.c_int64]
+        _lib.rvcx_convert_inflight.argtypes = [C.c_void_p]
+        _lib.rvcx_ticket_lead_ms.argtypes = [C.c_void_p, C.c_int64]
+        _lib.rvcx_ticket_lead_ms.restype = C.c_float
     return _lib
 
 
@@ -236,6 +246,58 @@ def make_table(state: dict):
         items.append(Tensor(nm, a.ctypes.data, dt, a.ndim, shp))
     arr = (Tensor * len(items))(*items)
     return arr, keep
+
+
+class Ticket:
+    """A conversion in flight (Context.convert_submit).  The object keeps every numpy array the library borrowed alive
+    until the ticket has been waited for; dropped unwaited, its finaliser waits."""
+
+    def __init__(self, ctx, tid, keep, outs, f32s, out_n):
+        self._ctx, self.id, self._keep = ctx, int(tid), keep
+        self._outs, self._f32s, self._out_n = outs, f32s, out_n
+        self._waited = False
+        self._lead = None
+
+    def done(self) -> bool:
+        """True when wait() will not block on the device"""
+        if self._waited:
+            return True
+        rc = lib().rvcx_convert_poll(self._ctx._h, self.id)
+        self._ctx._ck(0 if rc >= 0 else rc, "convert_poll")
+        return rc == 1
+
+    def wait(self):
+        """what Context.convert_batch returns for the same arguments"""
+        if self._waited:
+            raise RvcxError("Ticket.wait: the ticket has already been waited for")
+        self._waited = True
+        try:
+            self._ctx._ck(lib().rvcx_convert_wait(self._ctx._h, self.id), "convert_wait")
+            self._lead = float(lib().rvcx_ticket_lead_ms(self._ctx._h, self.id))
+            if self._outs is None:        # convert_submit_raw: the caller's own buffers hold the samples
+                return [int(v) for v in self._out_n]
+            pcm = [o[:self._out_n[i]].copy() for i, o in enumerate(self._outs)]
+            if self._f32s is not None:
+                return pcm, [o[:self._out_n[i]].copy() for i, o in enumerate(self._f32s)]
+            return pcm
+        finally:
+            self._keep = None      # the borrowed buffers are the caller's again
+
+    @property
+    def lead_ms(self) -> float:
+        """device ms between this ticket's first front-end work and the completion of the ticket submitted before it
+        (positive: they overlapped); valid after wait()"""
+        if self._lead is None:
+            raise RvcxError("Ticket.lead_ms is valid after wait()")
+        return self._lead
+
+    def __del__(self):
+        try:
+            if not self._waited and getattr(self._ctx, "_h", None):
+                self._waited = True
+                lib().rvcx_convert_wait(self._ctx._h, self.id)
+        except Exception:
+            pass
 
 
 class Context:
@@ -669,26 +731,27 @@ class Context:
     def noise_capacity(self, model_id, n, params) -> int:
         return int(lib().rvcx_noise_len(self._h, model_id, C.c_int64(n), C.byref(params)))
 
-    def convert_batch(self, model_id, wavs, params: "Params", noises=None, want_f32=False, inp_f0=None, crepe_dither=None):
-        """VC.pipeline for a list of 16 kHz mono clips -> list of int16 arrays (and the pre-quantisation
-        float waveforms when want_f32).  float64 clips (what the reference's load_audio returns) cross the
-        ABI as float64; anything else as float32.  Clips of one length class are converted as ragged micro-batches."""
+    def _convert_tables(self, what, model_id, wavs, params, noises, want_f32, inp_f0, crepe_dither):
+        """The argument tables of rvcx_convert_batch* / rvcx_convert_submit for a list of numpy clips.  float64 clips (what
+        the reference's load_audio returns) cross the ABI as float64; anything else as float32.  `keep` holds every array
+        the tables point into."""
         B = len(wavs)
-        is64 = B > 0 and all(np.asarray(w).dtype == np.float64 for w in wavs)
-        wavs = [np.ascontiguousarray(w, dtype=np.float64 if is64 else np.float32) for w in wavs]
-        ns = (C.c_int64 * B)(*[w.shape[0] for w in wavs])
-        wt = C.c_double if is64 else C.c_float
-        wp = (C.POINTER(wt) * B)(*[_p(w, wt) for w in wavs])
+        t = types.SimpleNamespace(B=B)
+        t.is64 = B > 0 and all(np.asarray(w).dtype == np.float64 for w in wavs)
+        wavs = [np.ascontiguousarray(w, dtype=np.float64 if t.is64 else np.float32) for w in wavs]
+        t.ns = (C.c_int64 * B)(*[w.shape[0] for w in wavs])
+        wt = C.c_double if t.is64 else C.c_float
+        t.wp = (C.POINTER(wt) * B)(*[_p(w, wt) for w in wavs])
         caps = [self.out_capacity(model_id, w.shape[0], params) for w in wavs]
         if any(c < 0 for c in caps):
-            raise RvcxError(f"convert_batch: no voice model with id {model_id} is resident in this context")
-        outs = [np.empty(c, np.int16) for c in caps]
-        op = (C.POINTER(C.c_int16) * B)(*[_p(o, C.c_int16) for o in outs])
-        f32s, fp = None, None
+            raise RvcxError(f"{what}: no voice model with id {model_id} is resident in this context")
+        t.outs = [np.empty(c, np.int16) for c in caps]
+        t.op = (C.POINTER(C.c_int16) * B)(*[_p(o, C.c_int16) for o in t.outs])
+        t.f32s, t.fp = None, None
         if want_f32:
-            f32s = [np.empty(c, np.float32) for c in caps]
-            fp = (C.POINTER(C.c_float) * B)(*[_p(o) for o in f32s])
-        nz, npp = None, None
+            t.f32s = [np.empty(c, np.float32) for c in caps]
+            t.fp = (C.POINTER(C.c_float) * B)(*[_p(o) for o in t.f32s])
+        nz, t.npp = None, None
         if noises is not None:
             nz = []
             for w, nv in zip(wavs, noises):
@@ -702,26 +765,67 @@ class Context:
                     raise RvcxError("noise longer than rvcx_noise_len")
                 buf[:nv.shape[0]] = nv
                 nz.append(buf)
-            npp = (C.POINTER(C.c_float) * B)(*[_p(b) for b in nz])
-        out_n = (C.c_int64 * B)()
+            t.npp = (C.POINTER(C.c_float) * B)(*[_p(b) for b in nz])
+        t.out_n = (C.c_int64 * B)()
+        t.ex, tabs, dith = None, None, None
         if inp_f0 is not None or crepe_dither is not None:
             # f0 files: (rows, 2) float32 tables of (time [s], f0 [Hz]) per utterance; crepe dither: one float per frame
-            tabs = [None if (inp_f0 is None or t is None) else np.ascontiguousarray(t, dtype=np.float32).reshape(-1, 2)
-                    for t in (inp_f0 if inp_f0 is not None else [None] * B)]
+            tabs = [None if (inp_f0 is None or x is None) else np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 2)
+                    for x in (inp_f0 if inp_f0 is not None else [None] * B)]
             dith = [None if (crepe_dither is None or d is None) else f32(d).ravel()
                     for d in (crepe_dither if crepe_dither is not None else [None] * B)]
-            ex = (UttExtra * B)(*[UttExtra(_p(t), 0 if t is None else t.shape[0], 0, _p(d), 0 if d is None else d.shape[0])
-                                  for t, d in zip(tabs, dith)])
-            wv = (C.c_void_p * B)(*[w.ctypes.data for w in wavs])
-            self._ck(lib().rvcx_convert_batch_ex(self._h, model_id, B, wv, 1 if is64 else 0, ns, C.byref(params), npp, ex,
-                                                 op, fp, out_n), "convert_batch_ex")
+            t.ex = (UttExtra * B)(*[UttExtra(_p(x), 0 if x is None else x.shape[0], 0, _p(d), 0 if d is None else d.shape[0])
+                                    for x, d in zip(tabs, dith)])
+        t.wv = (C.c_void_p * B)(*[w.ctypes.data for w in wavs])
+        t.keep = (wavs, nz, tabs, dith, t.outs, t.f32s, t.out_n, t.ns, t.wp, t.wv, t.op, t.fp, t.npp, t.ex)
+        return t
+
+    def convert_batch(self, model_id, wavs, params: "Params", noises=None, want_f32=False, inp_f0=None, crepe_dither=None):
+        """VC.pipeline for a list of 16 kHz mono clips -> list of int16 arrays (and the pre-quantisation
+        float waveforms when want_f32).  float64 clips (what the reference's load_audio returns) cross the
+        ABI as float64; anything else as float32.  Clips of one length class are converted as ragged micro-batches."""
+        t = self._convert_tables("convert_batch", model_id, wavs, params, noises, want_f32, inp_f0, crepe_dither)
+        if t.ex is not None:
+            self._ck(lib().rvcx_convert_batch_ex(self._h, model_id, t.B, t.wv, 1 if t.is64 else 0, t.ns, C.byref(params),
+                                                 t.npp, t.ex, t.op, t.fp, t.out_n), "convert_batch_ex")
         else:
-            fn = lib().rvcx_convert_batch_f64 if is64 else lib().rvcx_convert_batch
-            self._ck(fn(self._h, model_id, B, wp, ns, C.byref(params), npp, op, fp, out_n), "convert_batch")
-        pcm = [o[:out_n[i]].copy() for i, o in enumerate(outs)]
+            fn = lib().rvcx_convert_batch_f64 if t.is64 else lib().rvcx_convert_batch
+            self._ck(fn(self._h, model_id, t.B, t.wp, t.ns, C.byref(params), t.npp, t.op, t.fp, t.out_n), "convert_batch")
+        pcm = [o[:t.out_n[i]].copy() for i, o in enumerate(t.outs)]
         if want_f32:
-            return pcm, [o[:out_n[i]].copy() for i, o in enumerate(f32s)]
+            return pcm, [o[:t.out_n[i]].copy() for i, o in enumerate(t.f32s)]
         return pcm
+
+    def convert_submit(self, model_id, wavs, params: "Params", noises=None, want_f32=False, inp_f0=None,
+                       crepe_dither=None) -> "Ticket":
+        """convert_batch without the wait: enqueues the conversion and returns a Ticket; Ticket.wait() returns what
+        convert_batch returns.  Two tickets may be in flight per context (a third submit completes the oldest first)."""
+        t = self._convert_tables("convert_submit", model_id, wavs, params, noises, want_f32, inp_f0, crepe_dither)
+        tid = C.c_int64(0)
+        cast = lambda a: None if a is None else C.cast(a, C.c_void_p)  # noqa: E731
+        self._ck(lib().rvcx_convert_submit(self._h, model_id, t.B, cast(t.wv), 1 if t.is64 else 0, cast(t.ns), C.byref(params),
+                                           cast(t.npp), cast(t.ex), cast(t.op), cast(t.fp), cast(t.out_n), C.byref(tid)),
+                 "convert_submit")
+        return Ticket(self, tid.value, t.keep, t.outs, t.f32s, t.out_n)
+
+    def convert_submit_raw(self, model_id, wav_ptrs, ns, params, out_ptrs, f32_ptrs=None, noise_ptrs=None) -> "Ticket":
+        """convert_submit with raw (host or device) addresses of float32 clips, as convert_batch_raw takes them; the
+        caller keeps the buffers valid until Ticket.wait(), which returns the produced sample counts."""
+        B = len(wav_ptrs)
+        wp = (C.c_void_p * B)(*wav_ptrs)
+        op = (C.c_void_p * B)(*out_ptrs)
+        fp = None if f32_ptrs is None else (C.c_void_p * B)(*f32_ptrs)
+        npp = None if noise_ptrs is None else (C.c_void_p * B)(*noise_ptrs)
+        nn = (C.c_int64 * B)(*ns)
+        out_n = (C.c_int64 * B)()
+        tid = C.c_int64(0)
+        self._ck(lib().rvcx_convert_submit(self._h, model_id, B, wp, 0, nn, C.byref(params), npp, None, op, fp, out_n,
+                                           C.byref(tid)), "convert_submit")
+        return Ticket(self, tid.value, (out_n,), None, None, out_n)
+
+    def convert_inflight(self) -> int:
+        """tickets submitted and not yet completed on the device"""
+        return int(lib().rvcx_convert_inflight(self._h))
 
     def convert_batch_raw(self, model_id, wav_ptrs, ns, params, out_ptrs, f32_ptrs=None, noise_ptrs=None):
         """Same as convert_batch but with raw (host or device) addresses of float32 clips: nothing is staged

@@ -1,8 +1,12 @@
 // C ABI of librvcx.so (include/rvcx.h).  Nothing throws across this boundary.
 #include "../../include/rvcx.h"
 
+#include <atomic>
+#include <cmath>
 #include <cstdlib>
+#include <deque>
 #include <mutex>
+#include <unordered_map>
 
 #include "ctx.h"
 #include "layers.h"
@@ -17,10 +21,47 @@ using namespace rvcx;
 // thread of a process shares the one resident context (infer/_state.py) and ctypes releases the GIL -- so every entry
 // point takes the context's mutex (recursive: an entry point may call another).  Calls on one context QUEUE; throughput
 // comes from rvcx_convert_batch (one call, many utterances), not from threads.  Different contexts stay concurrent.
+// A conversion ticket (rvcx_convert_submit): the enqueue half of a conversion has run, the finish half runs when somebody
+// waits for it (or when something else needs the context to itself).  It owns copies of the small host-side arguments; the
+// audio, noise, dither and output buffers stay the caller's.
+struct Ticket {
+  rvcx_ticket id = 0;
+  enum State { InFlight, Done, Failed } state = InFlight;
+  std::string error;
+  int model_id = 0;
+  rvcx_params p;
+  std::vector<UttIO> ios;
+  std::vector<std::vector<float>> f0_rows;    // the f0-file tables `extra` pointed to
+  std::vector<int64_t> n_out;                 // produced samples per utterance (what out_n receives)
+  int64_t* out_n = nullptr;
+  bool inject_gru = false;                    // rvcx_debug_inject(1) was pending when the ticket was submitted: it is this ticket's
+  bool timing = false;
+  float ms[9] = {0};
+  TicketIO io;
+  ConvertStatePtr st;
+  bool enqueued = false;                      // ev_first / ev_done were recorded
+  std::shared_ptr<Ticket> prev;               // the ticket in flight in front of this one at submit time (lead_ms)
+  float lead_ms = 0.f;
+  std::vector<int> mbs;
+  std::vector<std::vector<long>> cuts;
+  ~Ticket() {
+    st.reset();
+    if (io.ev_first) (void)hipEventDestroy(io.ev_first);
+    if (io.ev_done) (void)hipEventDestroy(io.ev_done);
+  }
+};
+using TicketPtr = std::shared_ptr<Ticket>;
+
 struct rvcx_ctx {
   Ctx c;
   std::recursive_mutex mu;
+  std::deque<TicketPtr> inflight;                          // submit order; at most two
+  std::unordered_map<rvcx_ticket, TicketPtr> tickets;      // every ticket that has not been waited for
+  std::deque<std::pair<rvcx_ticket, float>> leads;         // lead_ms of the tickets waited for last
+  Arena load_arena;     // rvcx_resample_f64* with tickets in flight: a buffer nobody else uses (see there)
 };
+// ticket numbers are unique in the process: a ticket of another context is simply unknown here
+static std::atomic<int64_t> g_next_ticket{1};
 using CtxLock = std::unique_lock<std::recursive_mutex>;
 static CtxLock lock_ctx(rvcx_ctx* h) { return h ? CtxLock(h->mu) : CtxLock(); }
 
@@ -75,16 +116,13 @@ static void reset_after_failure(Ctx& c) {
   c.arena_hub.reset();
 }
 
+static void drain_tickets(rvcx_ctx* h);
+
+// the attempts of one call (see above); gru_plain: start on the single-workgroup GRU kernel (a ticket's re-run)
 template <typename F>
-static int api_call(rvcx_ctx* ctxp, bool repeat, F&& body) {
-  Ctx* C = ctxp ? &ctxp->c : nullptr;
-  CtxLock guard = lock_ctx(ctxp);
-  try {
-    if (!C) fail("null context");
-    RVCX_HIP(hipSetDevice(C->device));
-    if (!repeat) C->arena_budget = 0;     // loads / unloads change what is free: convert_micro_batch probes again
+static void run_attempts(Ctx* C, bool repeat, bool gru_plain, F&& body) {
+  {
     const int last = repeat ? kMaxAttempts - 1 : 0;
-    bool gru_plain = false;
     for (int attempt = 0; attempt <= last; ++attempt) {
       Fp32Scope fp32_scope(attempt > 0 && attempt == last);
       GruScope gru_scope(gru_plain);
@@ -108,6 +146,21 @@ static int api_call(rvcx_ctx* ctxp, bool repeat, F&& body) {
       if (attempt > 0 && attempt == last) (void)C->take_overflow();   // producers of split tensors may have re-raised the bit
       break;
     }
+  }
+}
+
+template <typename F>
+static int api_call(rvcx_ctx* ctxp, bool repeat, F&& body, bool drain = true) {
+  Ctx* C = ctxp ? &ctxp->c : nullptr;
+  CtxLock guard = lock_ctx(ctxp);
+  try {
+    if (!C) fail("null context");
+    RVCX_HIP(hipSetDevice(C->device));
+    // every entry point has the context to itself: tickets in flight complete first (they stay waitable).  The one
+    // exception is rvcx_resample_f64*, which brings its own memory and stream order (drain = false)
+    if (drain) drain_tickets(ctxp);
+    if (!repeat) C->arena_budget = 0;     // loads / unloads change what is free: convert_micro_batch probes again
+    run_attempts(C, repeat, false, body);
     return 0;
   } catch (const std::exception& e) {
     g_last_error = e.what();
@@ -214,10 +267,16 @@ int rvcx_create(int device, rvcx_ctx** out) {
     // RVCX_SERIAL=1: every launch on the one main stream (rocprofv3 kernel durations are then each launch's own)
     h->c.serial_env = getenv("RVCX_SERIAL") && atoi(getenv("RVCX_SERIAL")) != 0;
     h->c.serial = h->c.serial_env;
-    RVCX_HIP(hipMalloc(&h->c.dev_err, sizeof(int)));
-    RVCX_HIP(hipMemset(h->c.dev_err, 0, sizeof(int)));
-    RVCX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->c.err_host), sizeof(int), hipHostMallocDefault));
-    *h->c.err_host = 0;
+    RVCX_HIP(hipMalloc(&h->c.err_words, 3 * sizeof(int)));
+    RVCX_HIP(hipMemset(h->c.err_words, 0, 3 * sizeof(int)));
+    RVCX_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->c.err_words_host), 3 * sizeof(int), hipHostMallocDefault));
+    h->c.dev_err = h->c.err_words;
+    h->c.err_host = h->c.err_words_host;
+    for (int i = 0; i < 3; ++i) h->c.err_words_host[i] = 0;
+    for (int i = 0; i < 2; ++i) {
+      h->c.slot[i].err = h->c.err_words + 1 + i;
+      h->c.slot[i].err_host = h->c.err_words_host + 1 + i;
+    }
     h->c.arena.reserve((size_t)256 << 20);
     {
       // One-time work a serving process should not pay inside its first request (round 2: 88 ms in the first call's
@@ -241,6 +300,13 @@ int rvcx_create(int device, rvcx_ctx** out) {
 void rvcx_destroy(rvcx_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->c.device);
+  {
+    CtxLock guard = lock_ctx(ctx);
+    try {
+      drain_tickets(ctx);      // the callers' buffers receive what was in flight
+    } catch (const std::exception&) {
+    }
+  }
   (void)hipDeviceSynchronize();
   delete ctx;
 }
@@ -1485,13 +1551,27 @@ int64_t rvcx_noise_len(rvcx_ctx* ctx, int model_id, int64_t n, const rvcx_params
   return noise_len_for(ctx->c, *ctx->c.synths[model_id], n, *p);
 }
 
-static int convert_impl(rvcx_ctx* ctx, int model_id, int B, const float* const* wav32, const double* const* wav64,
-                        const int64_t* n, const rvcx_params* p, const float* const* noise, int16_t* const* out,
-                        float* const* out_f32, int64_t* out_n, const rvcx_utt_extra* extra = nullptr) {
-  API_BEGIN(ctx)
-  (void)get_synth(*C, model_id);
+static bool stage_timing_on() {
+  static const bool timing = !getenv("RVCX_STAGE_TIMING") || atoi(getenv("RVCX_STAGE_TIMING")) != 0;
+  return timing;
+}
+
+// one attempt of a synchronous conversion (the body api_call repeats)
+static void convert_run(Ctx* C, int model_id, std::vector<UttIO>& ios, const rvcx_params& p, int64_t* out_n) {
+  float ms[9] = {0};
+  convert_batch(*C, model_id, ios, p, stage_timing_on() ? ms : nullptr);
+  C->check_dev_err();
+  for (int k = 0; k < 9; ++k) C->timing[k] = ms[k];
+  if (out_n)
+    for (size_t i = 0; i < ios.size(); ++i) out_n[i] = ios[i].out_n;
+  C->arena.reset();
+}
+
+static void fill_ios(std::vector<UttIO>& ios, int B, const float* const* wav32, const double* const* wav64,
+                     const int64_t* n, const rvcx_params* p, const float* const* noise, int16_t* const* out,
+                     float* const* out_f32, const rvcx_utt_extra* extra) {
   if (B < 0 || (B > 0 && (!n || !p || !out || (!wav32 && !wav64)))) fail("convert_batch: null argument");
-  std::vector<UttIO> ios((size_t)B);
+  ios.assign((size_t)B, UttIO());
   for (int i = 0; i < B; ++i) {
     UttIO& u = ios[i];
     u.wav = wav32 ? wav32[i] : nullptr;
@@ -1509,14 +1589,16 @@ static int convert_impl(rvcx_ctx* ctx, int model_id, int B, const float* const* 
     }
     if (!(u.wav || u.wav64) || !u.out) fail("convert_batch: null buffer for utterance " + std::to_string(i));
   }
-  static const bool timing = !getenv("RVCX_STAGE_TIMING") || atoi(getenv("RVCX_STAGE_TIMING")) != 0;
-  float ms[9] = {0};
-  convert_batch(*C, model_id, ios, *p, timing ? ms : nullptr);
-  C->check_dev_err();
-  for (int k = 0; k < 9; ++k) C->timing[k] = ms[k];
-  if (out_n)
-    for (int i = 0; i < B; ++i) out_n[i] = ios[i].out_n;
-  C->arena.reset();
+}
+
+static int convert_impl(rvcx_ctx* ctx, int model_id, int B, const float* const* wav32, const double* const* wav64,
+                        const int64_t* n, const rvcx_params* p, const float* const* noise, int16_t* const* out,
+                        float* const* out_f32, int64_t* out_n, const rvcx_utt_extra* extra = nullptr) {
+  API_BEGIN(ctx)
+  (void)get_synth(*C, model_id);
+  std::vector<UttIO> ios;
+  fill_ios(ios, B, wav32, wav64, n, p, noise, out, out_f32, extra);
+  convert_run(C, model_id, ios, *p, out_n);
   API_END
 }
 
@@ -1541,6 +1623,248 @@ int rvcx_convert_batch_ex(rvcx_ctx* ctx, int model_id, int B, const void* const*
   return convert_impl(ctx, model_id, B, wav_is_f64 ? nullptr : reinterpret_cast<const float* const*>(wav16k),
                       wav_is_f64 ? reinterpret_cast<const double* const*>(wav16k) : nullptr, n, p, noise, out, out_f32,
                       out_n, extra);
+}
+
+// ------------------------------------------------------------------------------------------
+// conversion tickets: two requests in flight per context
+// ------------------------------------------------------------------------------------------
+// submit = the enqueue half of a conversion on the calling thread, wait = its finish half.  The second ticket's front end
+// (upload, high-pass, F0 model, HuBERT) runs on the front / HuBERT streams while the first is in its synthesizer on the main
+// stream, exactly as micro-batch k + 1 of one call does; tickets of different voice models or parameters take the same
+// path (nothing in the overlap depends on them being equal).  Completions are processed in submit order.
+
+// launches and error-word readers use this word for as long as the scope lives
+struct ErrWordScope {
+  Ctx& c;
+  int *d, *h;
+  ErrWordScope(Ctx& cc, int* dev, int* host) : c(cc), d(cc.dev_err), h(cc.err_host) {
+    c.dev_err = dev;
+    c.err_host = host;
+  }
+  ~ErrWordScope() {
+    c.dev_err = d;
+    c.err_host = h;
+  }
+};
+
+// the oldest ticket in flight: wait for the device, then either take its results or -- range guard, BiGRU time-out --
+// repeat it (and what depends on it) the way the same requests would have run as synchronous calls in submit order
+static void settle_oldest(rvcx_ctx* h) {
+  Ctx& c = h->c;
+  TicketPtr T = h->inflight.front();
+  RVCX_HIP(hipSetDevice(c.device));
+  if (T->st) RVCX_HIP(hipEventSynchronize(T->io.ev_done));
+  if (T->prev) {
+    if (T->enqueued && T->prev->enqueued) (void)hipEventElapsedTime(&T->lead_ms, T->io.ev_first, T->prev->io.ev_done);
+    (void)hipGetLastError();
+    T->prev.reset();
+  }
+  int v = T->st ? *c.slot[T->io.slot].err_host : 0;
+  if (T->inject_gru) v |= kErrGruTimeout;
+  if (!(v & (kErrGruTimeout | kErrH3Overflow))) {
+    h->inflight.pop_front();
+    try {
+      if (T->st) {
+        convert_finish(c, *T->st, T->timing ? T->ms : nullptr);
+        const char* stage = c.slot[T->io.slot].stage;
+        for (const auto& sg : T->io.staged) memcpy(sg.dst, stage + sg.off, sg.bytes);
+        T->mbs = convert_state_mbs(*T->st);
+        T->cuts = convert_state_cuts(*T->st);
+      }
+      for (size_t i = 0; i < T->ios.size(); ++i) T->n_out[i] = T->ios[i].out_n;
+      if (T->out_n)
+        for (size_t i = 0; i < T->ios.size(); ++i) T->out_n[i] = T->n_out[i];
+      T->state = Ticket::Done;
+    } catch (const std::exception& e) {
+      T->state = Ticket::Failed;
+      T->error = e.what();
+    }
+    T->st.reset();
+    if (h->inflight.empty()) c.arena.reset();     // the work area is nobody's now (a synchronous call may grow the arena)
+    return;
+  }
+  // Everything in flight completes; then the affected tickets run again through the synchronous path, oldest first.  An
+  // overflow pins a layer, and a pin changes which kernels later requests run on: every later ticket was enqueued before
+  // the pin and is repeated as well, whatever its own word says.  A BiGRU time-out changes no lasting state: this ticket only.
+  RVCX_HIP(hipDeviceSynchronize());
+  std::vector<TicketPtr> redo{T};
+  if (v & kErrH3Overflow)
+    for (size_t i = 1; i < h->inflight.size(); ++i) redo.push_back(h->inflight[i]);
+  for (WeightRegion* r : all_regions(c, nullptr)) r->clear_overflow();    // the layers' stamp words are shared by both tickets
+  ErrWordScope words(c, c.err_words, c.err_words_host);
+  const bool pending_inject = c.inject_gru_timeout;     // belongs to the NEXT request (a submit that is settling us first)
+  for (const TicketPtr& R : redo) {
+    for (auto it = h->inflight.begin(); it != h->inflight.end(); ++it)
+      if (*it == R) {
+        h->inflight.erase(it);
+        break;
+      }
+    if (R->st) RVCX_HIP(hipMemset(c.slot[R->io.slot].err, 0, sizeof(int)));
+    R->st.reset();
+    R->prev.reset();
+    const bool plain = R == T && (v & kErrGruTimeout);
+    c.inject_gru_timeout = R != T && R->inject_gru;     // a later ticket's own injected time-out: its repeat meets it
+    if (plain) c.gru_fallbacks++;
+    try {
+      run_attempts(&c, true, plain, [&](Ctx* C) { convert_run(C, R->model_id, R->ios, R->p, R->out_n); });
+      for (size_t i = 0; i < R->ios.size(); ++i) R->n_out[i] = R->ios[i].out_n;
+      R->mbs = c.last_mbs;
+      R->cuts = c.last_cuts;
+      for (int k = 0; k < 9; ++k) R->ms[k] = c.timing[k];
+      R->state = Ticket::Done;
+    } catch (const std::exception& e) {
+      R->state = Ticket::Failed;
+      R->error = e.what();
+      reset_after_failure(c);
+      (void)hipGetLastError();
+    }
+  }
+  c.inject_gru_timeout = pending_inject;
+}
+
+static void drain_tickets(rvcx_ctx* h) {
+  while (h && !h->inflight.empty()) settle_oldest(h);
+}
+
+static int ticket_error(rvcx_ctx* ctx, const std::string& what) {
+  g_last_error = what;
+  if (ctx) ctx->c.last_error = what;
+  return -1;
+}
+
+int rvcx_convert_submit(rvcx_ctx* ctx, int model_id, int B, const void* const* wav16k, int wav_is_f64, const int64_t* n,
+                        const rvcx_params* p, const float* const* noise, const rvcx_utt_extra* extra, int16_t* const* out,
+                        float* const* out_f32, int64_t* out_n, rvcx_ticket* ticket) {
+  CtxLock guard = lock_ctx(ctx);
+  if (!ctx) return ticket_error(nullptr, "null context");
+  Ctx& c = ctx->c;
+  bool inject = false;
+  int slot = -1;
+  try {
+    if (!ticket) fail("convert_submit: null ticket pointer");
+    RVCX_HIP(hipSetDevice(c.device));
+    (void)get_synth(c, model_id);
+    TicketPtr T = std::make_shared<Ticket>();
+    fill_ios(T->ios, B, wav_is_f64 ? nullptr : reinterpret_cast<const float* const*>(wav16k),
+             wav_is_f64 ? reinterpret_cast<const double* const*>(wav16k) : nullptr, n, p, noise, out, out_f32, extra);
+    T->f0_rows.resize((size_t)B);
+    for (int i = 0; i < B; ++i)
+      if (T->ios[i].inp_f0 && T->ios[i].inp_f0_rows > 0) {      // the f0-file rows are copied; the big buffers are borrowed
+        T->f0_rows[i].assign(T->ios[i].inp_f0, T->ios[i].inp_f0 + 2 * (size_t)T->ios[i].inp_f0_rows);
+        T->ios[i].inp_f0 = T->f0_rows[i].data();
+      }
+    T->model_id = model_id;
+    T->p = *p;
+    T->out_n = out_n;
+    T->n_out.assign((size_t)B, 0);
+    T->timing = stage_timing_on();
+    // two front sets, two event sets, two slots: a third ticket first completes the oldest one (it stays waitable)
+    while (ctx->inflight.size() >= 2) settle_oldest(ctx);
+    T->io.slot = ctx->inflight.empty() ? 0 : 1 - ctx->inflight.back()->io.slot;
+    T->io.beside_predecessor = !ctx->inflight.empty();
+    if (!ctx->inflight.empty()) T->prev = ctx->inflight.back();
+    T->io.drain = [ctx] { drain_tickets(ctx); };
+    RVCX_HIP(hipEventCreate(&T->io.ev_first));
+    RVCX_HIP(hipEventCreate(&T->io.ev_done));
+    inject = c.inject_gru_timeout;
+    T->inject_gru = inject;
+    c.inject_gru_timeout = false;
+    {
+      Ctx::TicketSlot& sl = c.slot[T->io.slot];
+      slot = T->io.slot;
+      ErrWordScope words(c, sl.err, sl.err_host);
+      c.launch_seq = 0;
+      c.err_snapshot = false;
+      *sl.err_host = 0;
+      T->st = convert_enqueue(c, model_id, T->ios, T->p, T->timing, &T->io);
+      T->enqueued = T->st != nullptr;
+    }
+    T->id = g_next_ticket.fetch_add(1);
+    ctx->inflight.push_back(T);
+    ctx->tickets[T->id] = T;
+    *ticket = T->id;
+    return 0;
+  } catch (const std::exception& e) {
+    // whatever was enqueued for the failed ticket runs out (reset_after_failure waits for the device); a ticket already
+    // in flight keeps its slot and is settled by its own wait
+    c.inject_gru_timeout = c.inject_gru_timeout || inject;
+    ticket_error(ctx, e.what());
+    reset_after_failure(c);
+    // launches of the failed ticket may have raised the slot's word: the next ticket of that slot must not inherit it
+    if (slot >= 0) (void)hipMemset(c.slot[slot].err, 0, sizeof(int));
+    (void)hipGetLastError();
+    return -1;
+  }
+}
+
+int rvcx_convert_wait(rvcx_ctx* ctx, rvcx_ticket t) {
+  CtxLock guard = lock_ctx(ctx);
+  if (!ctx) return ticket_error(nullptr, "null context");
+  static const char* kUnknown = "convert_wait: unknown ticket (already waited for, or a ticket of another context)";
+  try {
+    auto it = ctx->tickets.find(t);
+    if (it == ctx->tickets.end()) return ticket_error(ctx, kUnknown);
+    TicketPtr T = it->second;
+    if (T->state == Ticket::InFlight && T->st) {
+      // block on the device WITHOUT the context's mutex: another thread's submit must be able to fill the pipeline
+      hipEvent_t ev = T->io.ev_done;
+      guard.unlock();
+      (void)hipSetDevice(ctx->c.device);
+      const hipError_t rc = hipEventSynchronize(ev);
+      guard.lock();
+      if (rc != hipSuccess) fail(std::string("convert_wait: ") + hipGetErrorString(rc));
+    }
+    it = ctx->tickets.find(t);
+    if (it == ctx->tickets.end()) return ticket_error(ctx, kUnknown);   // another thread waited for it meanwhile
+    while (T->state == Ticket::InFlight) {        // completions settle in submit order: everything older goes first
+      if (ctx->inflight.empty()) fail("internal: a ticket in flight is not in the list");
+      settle_oldest(ctx);
+    }
+    ctx->tickets.erase(it);
+    Ctx& c = ctx->c;
+    c.last_mbs = T->mbs;
+    c.last_cuts = T->cuts;
+    for (int k = 0; k < 9; ++k) c.timing[k] = T->ms[k];
+    ctx->leads.emplace_back(T->id, T->lead_ms);
+    if (ctx->leads.size() > 256) ctx->leads.pop_front();
+    if (T->state == Ticket::Failed) return ticket_error(ctx, T->error);
+    return 0;
+  } catch (const std::exception& e) {
+    return ticket_error(ctx, e.what());
+  }
+}
+
+int rvcx_convert_poll(rvcx_ctx* ctx, rvcx_ticket t) {
+  CtxLock guard = lock_ctx(ctx);
+  if (!ctx) return ticket_error(nullptr, "null context");
+  auto it = ctx->tickets.find(t);
+  if (it == ctx->tickets.end()) return ticket_error(ctx, "convert_poll: unknown ticket");
+  const Ticket& T = *it->second;
+  if (T.state != Ticket::InFlight || !T.st) return 1;
+  (void)hipSetDevice(ctx->c.device);
+  const hipError_t rc = hipEventQuery(T.io.ev_done);
+  if (rc == hipSuccess) return 1;
+  (void)hipGetLastError();
+  return rc == hipErrorNotReady ? 0 : ticket_error(ctx, std::string("convert_poll: ") + hipGetErrorString(rc));
+}
+
+int rvcx_convert_inflight(rvcx_ctx* ctx) {
+  CtxLock guard = lock_ctx(ctx);
+  if (!ctx) return -1;
+  (void)hipSetDevice(ctx->c.device);
+  int k = 0;
+  for (const TicketPtr& T : ctx->inflight)
+    if (T->st && hipEventQuery(T->io.ev_done) != hipSuccess) ++k;
+  (void)hipGetLastError();
+  return k;
+}
+
+float rvcx_ticket_lead_ms(rvcx_ctx* ctx, rvcx_ticket t) {
+  CtxLock guard = lock_ctx(ctx);
+  if (!ctx) return NAN;
+  for (auto it = ctx->leads.rbegin(); it != ctx->leads.rend(); ++it)
+    if (it->first == t) return it->second;
+  return NAN;
 }
 
 int rvcx_micro_batch(rvcx_ctx* ctx, int model_id, int64_t n, const rvcx_params* p) {
@@ -1691,20 +2015,27 @@ int64_t rvcx_resample_len(int64_t n, int sr_in, int sr_out) {
 
 int rvcx_resample_f64_kind(rvcx_ctx* ctx, const double* x, int64_t frames, int channels, int sr_in, int sr_out, int kind,
                            double* y) {
-  API_BEGIN(ctx)
-  if (!x || !y || frames <= 0 || channels < 1 || sr_in <= 0 || sr_out <= 0) fail("resample: bad argument");
-  const long n_out = resample_out_len((long)frames, sr_in, sr_out);
-  C->arena.reserve(((size_t)frames * channels + (size_t)n_out) * 8 + ((size_t)8 << 20));
-  C->arena.reset();
-  hipStream_t s = C->stream;
-  double* dx = any_to_dev(*C, x, (size_t)frames * channels);
-  double* dy = C->arena.alloc<double>((size_t)std::max<long>(n_out, 1));
-  const ResampleFilter f = make_resample_filter(C->arena, sr_in, sr_out, s, kind);
-  launch_resample_f64(f, dx, (long)frames, channels, dy, n_out, s);
-  RVCX_HIP(hipMemcpyAsync(y, dy, (size_t)n_out * 8, hipMemcpyDefault, s));
-  RVCX_HIP(hipStreamSynchronize(s));
-  C->arena.reset();
-  API_END
+  // load_audio's resampler is what a "convert this folder" loop calls BETWEEN two submits (the next file is decoded while
+  // two tickets are in flight), so it does not complete the tickets: with tickets in flight it works in a buffer of its own
+  // (nothing a ticket uses is touched or moved) on the front stream, whose work for the tickets in flight ended long ago,
+  // so that it runs beside their synthesizer instead of behind it.  Same kernels, same bits as on an idle context.
+  return api_call(ctx, true, [&](Ctx* C) {
+    if (!x || !y || frames <= 0 || channels < 1 || sr_in <= 0 || sr_out <= 0) fail("resample: bad argument");
+    const bool beside = !ctx->inflight.empty();
+    Arena& A = beside ? ctx->load_arena : C->arena;
+    hipStream_t s = (beside && !C->serial) ? C->stream2 : C->stream;
+    const long n_out = resample_out_len((long)frames, sr_in, sr_out);
+    A.reset();
+    A.reserve(((size_t)frames * channels + (size_t)n_out) * 8 + ((size_t)8 << 20));
+    double* dx = A.alloc<double>((size_t)frames * channels);
+    RVCX_HIP(hipMemcpyAsync(dx, x, (size_t)frames * channels * sizeof(double), hipMemcpyDefault, s));
+    double* dy = A.alloc<double>((size_t)std::max<long>(n_out, 1));
+    const ResampleFilter f = make_resample_filter(A, sr_in, sr_out, s, kind);
+    launch_resample_f64(f, dx, (long)frames, channels, dy, n_out, s);
+    RVCX_HIP(hipMemcpyAsync(y, dy, (size_t)n_out * 8, hipMemcpyDefault, s));
+    RVCX_HIP(hipStreamSynchronize(s));
+    A.reset();
+  }, /*drain=*/false);
 }
 
 int rvcx_resample_f64(rvcx_ctx* ctx, const double* x, int64_t frames, int channels, int sr_in, int sr_out, double* y) {

@@ -218,6 +218,19 @@ struct Ctx {
   long fp32_reruns = 0;           // calls repeated because of that (each repeat pins one layer to fp32, or, last resort, all)
   long gru_fallbacks = 0;         // calls repeated with the single-workgroup BiGRU kernel after a cluster time-out
   bool inject_gru_timeout = false;
+  // ---- conversion tickets (rvcx_convert_submit, api.hip): at most two in flight, each in a slot of its own.  A slot owns
+  // what a ticket needs for its whole life (PCM, float waveform, parity noise, f0-file track, both front sets), a device
+  // error word with its pinned host copy (dev_err points at the word of the ticket being enqueued, at words[0] otherwise: an
+  // overflow or a GRU time-out is then attributed to the ticket that raised it), and pinned staging for the outputs.
+  struct TicketSlot {
+    Arena arena;
+    int* err = nullptr;         // err_words + 1 + slot
+    int* err_host = nullptr;    // err_words_host + 1 + slot
+    char* stage = nullptr;      // pinned host memory the outputs leave into; copied to the caller's buffers on completion
+    size_t stage_cap = 0;
+  } slot[2];
+  int* err_words = nullptr;       // device: {synchronous calls, slot 0, slot 1}
+  int* err_words_host = nullptr;  // pinned: the same three
   int launch_seq = 0;             // launches of split-fp16 kernels since the call began (orders the layers' overflow stamps)
   float timing[9] = {0};
   std::vector<int> last_mbs;      // member counts of the micro-batches of the last convert_batch call

@@ -99,8 +99,10 @@ Ctx::~Ctx() {
   index.reset();
   if (timer.made)
     for (auto& e : timer.ev) (void)hipEventDestroy(e);
-  if (dev_err) (void)hipFree(dev_err);
-  if (err_host) (void)hipHostFree(err_host);
+  if (err_words) (void)hipFree(err_words);
+  if (err_words_host) (void)hipHostFree(err_words_host);
+  for (auto& sl : slot)
+    if (sl.stage) (void)hipHostFree(sl.stage);
   for (auto* p : splitk_buf)
     if (p) (void)hipFree(p);
   if (ev_fork) (void)hipEventDestroy(ev_fork);

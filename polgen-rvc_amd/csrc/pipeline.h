@@ -1,6 +1,7 @@
 // VC.pipeline orchestration (rvc/infer/pipeline.py:289-467).
 #pragma once
 #include <functional>
+#include <memory>
 #include "models.h"
 
 namespace rvcx {
@@ -51,6 +52,37 @@ struct F0Extra {
   long dither_n = 0;
   int seed_offset = 0;
 };
+// A conversion in two halves.  convert_enqueue plans the call and enqueues ALL of its device work; convert_finish runs once
+// the device has completed it and resolves the stage times.  convert_batch (the synchronous call) is one after the other
+// with the stream synchronisations in between; a ticket (rvcx_convert_submit) returns to its caller between the two.
+struct ConvertState;      // what the enqueue half leaves for the finish half (pipeline.hip)
+struct ConvertStateDeleter {
+  void operator()(ConvertState*) const;
+};
+using ConvertStatePtr = std::unique_ptr<ConvertState, ConvertStateDeleter>;
+// The ticket a conversion is enqueued for.  Its ticket-long buffers and front sets come from Ctx::slot[slot].arena (the
+// main arena keeps the work area only, reused from ticket to ticket in stream order), outputs bound for plain host memory
+// leave into the slot's pinned staging (`staged`: copied to the caller's buffers once the device is done -- an
+// asynchronous copy into pageable memory would hold the enqueueing thread until the ticket has finished), ev_first /
+// ev_done bracket the ticket on the device, and nothing in the enqueue half waits for the device except `drain`.
+struct TicketIO {
+  int slot = 0;
+  hipEvent_t ev_first = nullptr;    // front stream, ahead of the ticket's first front-end work
+  hipEvent_t ev_done = nullptr;     // main stream, behind its last copy
+  bool beside_predecessor = false;  // another ticket is in flight: this front end runs beside that ticket's decoder
+  std::function<void()> drain;      // completes every ticket in flight; called before memory they may use is freed or moved
+  struct Staged {
+    void* dst;
+    size_t off, bytes;              // offset into the slot's staging
+  };
+  std::vector<Staged> staged;
+};
+ConvertStatePtr convert_enqueue(Ctx& c, int model_id, std::vector<UttIO>& utts, const rvcx_params& p, bool timing,
+                                TicketIO* ticket /*null: a synchronous call*/);
+void convert_finish(Ctx& c, ConvertState& st, float* stage_ms /*9 or null*/);
+// the micro-batch sizes and cut points of the conversion (what rvcx_last_micro_batches / rvcx_last_cuts report)
+const std::vector<int>& convert_state_mbs(const ConvertState& st);
+const std::vector<std::vector<long>>& convert_state_cuts(const ConvertState& st);
 // VC.pipeline for a list of utterances: equal-length utterances run as micro-batches (B > 1 through every network).
 void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& utts, const rvcx_params& p, float* stage_ms /*9 or null*/);
 int convert_micro_batch(Ctx& c, int model_id, long n, const rvcx_params& p);   // utterances per micro-batch at this length

@@ -428,9 +428,11 @@ long noise_len_for(const Ctx& c, const SynthModel& m, long n, const rvcx_params&
 namespace {
 
 struct StageClock {
-  bool on;
+  bool on = false;
   std::vector<hipEvent_t> ev;
-  explicit StageClock(bool enabled) : on(enabled) {}
+  StageClock() = default;
+  StageClock(const StageClock&) = delete;
+  StageClock& operator=(const StageClock&) = delete;
   int mark(hipStream_t s) {
     if (!on) return -1;
     hipEvent_t e;
@@ -477,6 +479,42 @@ struct Job {                  // one vc() call of the reference: chunk `ci` of u
 };
 
 }  // namespace
+
+// Everything of a conversion that outlives its enqueue half: the event timeline and what the stage times are read from,
+// the host copies of the f0-file tracks (uploaded asynchronously), and the call's micro-batch / cut-point record.
+struct ConvertState {
+  StageClock clk;
+  struct Span {
+    int a, b;
+    float* acc;
+  };
+  std::vector<Span> spans;
+  float t_hp = 0, t_f0 = 0, t_hub = 0, t_idx = 0, t_syn[3] = {0, 0, 0}, t_post = 0, t_wait_hub = 0, t_wait_f0 = 0;
+  std::vector<int> f0_ev0, f0_ev1, hub_ev0, hub_ev1;
+  std::vector<std::array<hipEvent_t, 4>> syn_ev;   // synth_forward's own stage events
+  int e_begin = -1, e_end = -1, mid_mark = -1;
+  size_t n_mbs = 0;
+  std::vector<std::vector<double>> f0_tracks;
+  std::vector<int> last_mbs;
+  std::vector<std::vector<long>> last_cuts;
+  ~ConvertState() {
+    for (auto& ev : syn_ev)
+      for (auto& e : ev) (void)hipEventDestroy(e);
+  }
+};
+void ConvertStateDeleter::operator()(ConvertState* st) const { delete st; }
+const std::vector<int>& convert_state_mbs(const ConvertState& st) { return st.last_mbs; }
+const std::vector<std::vector<long>>& convert_state_cuts(const ConvertState& st) { return st.last_cuts; }
+
+// may an asynchronous copy write to p without staging: device memory, or host memory HIP knows (pinned / registered)
+static bool host_visible_to_device(const void* p) {
+  hipPointerAttribute_t pa;
+  if (hipPointerGetAttributes(&pa, p) != hipSuccess) {
+    (void)hipGetLastError();                   // plain host memory is not known to HIP
+    return false;
+  }
+  return pa.type == hipMemoryTypeDevice || pa.type == hipMemoryTypeHost || pa.type == hipMemoryTypeManaged;
+}
 
 size_t convert_item_bytes(Ctx& c, int model_id, long n, const rvcx_params& p) {
   // arena bytes one utterance of a micro-batch needs beyond the call-long buffers (front set x2 + work area)
@@ -552,7 +590,8 @@ int convert_micro_batch(Ctx& c, int model_id, long n, const rvcx_params& p) {
       if (cur != c.device) (void)hipSetDevice(c.device);
       size_t free_b = 0, total_b = 0;
       if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) {
-        const size_t mine = c.arena.capacity() + c.arena_f0.capacity() + c.arena_hub.capacity();
+        const size_t mine = c.arena.capacity() + c.arena_f0.capacity() + c.arena_hub.capacity() +
+                            c.slot[0].arena.capacity() + c.slot[1].arena.capacity();
         c.arena_budget = std::max<size_t>(1, std::min(budget, (size_t)((double)(free_b + mine) * 0.7)));
       } else {
         c.arena_budget = budget;
@@ -661,6 +700,23 @@ long get_f0_device(Ctx& c, const float* apad, long n_pad, const rvcx_params& p, 
 // its CU-masked stream; finished PCM leaves behind its micro-batch on the main stream.  No host synchronisation inside the
 // loop; the cut search of clips longer than x_max seconds runs on host threads and is joined before HuBERT is enqueued.
 void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_params& p, float* stage_ms) {
+  ConvertStatePtr st = convert_enqueue(c, model_id, ios, p, stage_ms != nullptr, nullptr);
+  if (!st) return;
+  hipStream_t s = c.stream;
+  hipStream_t sf = c.serial ? s : c.stream2;
+  hipStream_t sio = (c.serial || !c.stream_io) ? s : c.stream_io;
+  // the device error word travels with the call's own synchronisation (Ctx::snapshot_dev_err): every kernel that can set it
+  // has been joined into the main stream by now (F0 and HuBERT streams through ev_join / ev_hubdone, the branch streams
+  // at each stage's end)
+  c.snapshot_dev_err(s);
+  RVCX_HIP(hipStreamSynchronize(s));
+  if (sf != s) RVCX_HIP(hipStreamSynchronize(sf));
+  if (sio != s) RVCX_HIP(hipStreamSynchronize(sio));
+  convert_finish(c, *st, stage_ms);
+}
+
+ConvertStatePtr convert_enqueue(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_params& p, bool timing,
+                                TicketIO* ticket) {
   RVCX_CHECK(c.hubert != nullptr, "convert: hubert not loaded");
   check_f0_backend(c, p);
   RVCX_CHECK(model_id >= 0 && model_id < (int)c.synths.size() && c.synths[model_id], "convert: bad model id");
@@ -673,12 +729,19 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   RVCX_CHECK(E == c.hubert->cfg.embed_dim || (c.hubert->has_final_proj && E == c.hubert->final_proj.cout),
              "the voice model's input_dim is neither the HuBERT's embed_dim (v2) nor its final_proj width (v1)");
   const int NB = (int)ios.size();
-  if (NB == 0) return;
+  if (NB == 0) return nullptr;
+  ConvertStatePtr stp(new ConvertState());
+  ConvertState& st = *stp;
   hipStream_t s = c.stream;
   hipStream_t sf = c.serial ? s : c.stream2;
   hipStream_t sio = (c.serial || !c.stream_io) ? s : c.stream_io;   // copy-out stream (the main stream: see ctx.h)
   Arena& A = c.arena;
-  StageClock clk(stage_ms != nullptr);
+  // ticket-long buffers (PCM, float waveform, parity noise, f0-file track) and the two front sets: below work_mark of the
+  // main arena in a synchronous call, in the ticket's own slot otherwise -- the previous ticket may still be reading its own
+  Arena& L = ticket ? c.slot[ticket->slot].arena : c.arena;
+  StageClock& clk = st.clk;
+  clk.on = timing;
+  const bool stage_ms = timing;
 
   // ---- micro-batches: utterances sorted by length (stable); utterances of one length class (bucket_length: the same
   // launch geometry `nd`) are grouped, at most `mb_max` per group.  `ragged`: the members differ from nd.
@@ -710,9 +773,6 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     }
     i = j;
   }
-  c.last_mbs.clear();
-  for (const auto& mb : mbs) c.last_mbs.push_back(mb.count);
-  c.last_cuts.assign(NB, {});
   size_t call_bytes = 0, mb_bytes = 0, f0_bytes = 0, hub_bytes = 0;
   for (const auto& u : ios) {
     any_f64 |= u.wav64 != nullptr;
@@ -732,20 +792,58 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   }
   (void)any_f64;
   (void)any_noise;
-  c.ensure_splitk((int)std::max<size_t>(1, [&] {
+  const int mb_items = [&] {
     int m = 1;
     for (const auto& mb : mbs) m = std::max(m, mb.count);
-    return (size_t)m;
-  }()));
-  A.reserve(call_bytes + mb_bytes + ((size_t)96 << 20));
-  A.reset();
+    return m;
+  }();
+  // the two front sets' sizes (allocated below)
+  size_t front_items = 0;
+  size_t wmax = 0, emax = 0, nmax = 0, pmax = 0, fmax = 0, hmax = 0;
+  for (const auto& mb : mbs) {
+    const long n = mb.nd;
+    const size_t k = (size_t)mb.count;
+    front_items = std::max(front_items, k);
+    wmax = std::max(wmax, k * (size_t)n * 8);
+    emax = std::max(emax, k * highpass_ext_doubles(n));
+    nmax = std::max(nmax, k * (size_t)n);
+    pmax = std::max(pmax, k * (size_t)(n + 2 * g.t_pad));
+    fmax = std::max(fmax, k * (size_t)((n + 2 * g.t_pad) / 160 + 8));
+    // every chunk carries 2 * t_pad samples of context beyond its share of the clip
+    hmax = std::max(hmax, k * (size_t)E * (size_t)((n + 2 * g.t_pad + (cut_count(n, g) + 1) * (2 * g.t_pad + 640)) / 320 + 8));
+  }
+  if (ticket) {
+    // what the slot holds: the call-long buffers and both front sets (every allocation rounds up to 256 bytes)
+    const size_t front_bytes = 2 * (wmax + emax * 8 + nmax * 12 + pmax * 4 + fmax * 8 + hmax * 4 + front_items * 4 + 9 * 256);
+    const size_t slot_bytes = call_bytes + front_bytes + (size_t)NB * 8 * 256 + ((size_t)8 << 20);
+    // Memory that a ticket in flight uses is never freed or moved under it: if anything has to grow, the tickets in flight
+    // complete first (they stay waitable).  The work area, the F0 and the HuBERT arenas are shared by consecutive tickets
+    // and reused in stream order, exactly as consecutive micro-batches of one call reuse them.
+    // (the slot's own arena may grow as it is: its previous ticket has completed and nobody else uses it)
+    const bool grow = mb_items > c.splitk_items || mb_bytes + ((size_t)96 << 20) > A.capacity() ||
+                      f0_bytes + ((size_t)64 << 20) > c.arena_f0.capacity() || hub_bytes + ((size_t)64 << 20) > c.arena_hub.capacity();
+    if (grow && ticket->drain) ticket->drain();
+    c.ensure_splitk(mb_items);
+    A.reset();
+    A.reserve(mb_bytes + ((size_t)96 << 20));
+    L.reset();
+    L.reserve(slot_bytes);
+  } else {
+    c.ensure_splitk(mb_items);
+    A.reserve(call_bytes + mb_bytes + ((size_t)96 << 20));
+    A.reset();
+  }
   c.arena_f0.reset();
   c.arena_f0.reserve(f0_bytes + ((size_t)64 << 20));
   c.arena_hub.reset();
   c.arena_hub.reserve(hub_bytes + ((size_t)64 << 20));
+  c.last_mbs.clear();      // (behind the drain above: completing a ticket may repeat it as a synchronous call)
+  for (const auto& mb : mbs) c.last_mbs.push_back(mb.count);
+  c.last_cuts.assign(NB, {});
+  if (ticket && ticket->ev_first) RVCX_HIP(hipEventRecord(ticket->ev_first, sf));
 
   // ---- call-long buffers
-  std::vector<std::vector<double>> f0_tracks;      // host copies stay alive until the call's last synchronisation
+  std::vector<std::vector<double>>& f0_tracks = st.f0_tracks;      // host copies stay alive until the call's last synchronisation
   f0_tracks.reserve(NB);
   std::vector<Utt> utts(NB);
   for (int i = 0; i < NB; ++i) {
@@ -755,21 +853,35 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     u.n_pad = u.n + 2 * g.t_pad;
     u.p_len = u.n_pad / 160;
     u.cap = out_capacity(M, u.n, p);
-    u.pcm = A.alloc<short>((size_t)u.cap);
-    u.outf = A.alloc<float>((size_t)u.cap);
+    u.pcm = L.alloc<short>((size_t)u.cap);
+    u.outf = L.alloc<float>((size_t)u.cap);
     if (ios[i].noise) {
       u.noise_cap = noise_len_for(c, M, u.n, p);
-      u.noise = A.alloc<float>((size_t)u.noise_cap);
+      u.noise = L.alloc<float>((size_t)u.noise_cap);
     }
     if (ios[i].inp_f0 && ios[i].inp_f0_rows > 0) {       // f0 file: the replacement track, built like the reference does
       f0_tracks.push_back(f0_file_track(ios[i].inp_f0, ios[i].inp_f0_rows));
       const std::vector<double>& tr = f0_tracks.back();
       if (!tr.empty()) {
         u.rep_n = (int)tr.size();
-        u.rep = A.alloc<double>(tr.size());
+        u.rep = L.alloc<double>(tr.size());
         RVCX_HIP(hipMemcpyAsync(u.rep, tr.data(), tr.size() * sizeof(double), hipMemcpyHostToDevice, sf));
       }
     }
+  }
+  size_t stage_off = 0;
+  if (ticket) {       // pinned staging for every output of the ticket (the slot's previous ticket has completed)
+    Ctx::TicketSlot& sl = c.slot[ticket->slot];
+    size_t need = 0;
+    for (int i = 0; i < NB; ++i) need += (size_t)utts[i].cap * 6 + 512;
+    if (need > sl.stage_cap) {
+      if (sl.stage) (void)hipHostFree(sl.stage);
+      sl.stage = nullptr;
+      sl.stage_cap = 0;
+      RVCX_HIP(hipHostMalloc(reinterpret_cast<void**>(&sl.stage), need, hipHostMallocDefault));
+      sl.stage_cap = need;
+    }
+    ticket->staged.clear();
   }
   // two front sets (micro-batch k+1's front end runs while k is in the synthesizer)
   struct Front {
@@ -781,47 +893,27 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     size_t feats_cap = 0;
     int* ns = nullptr;          // device: the members' sample counts (ragged micro-batches)
   } fr[2];
-  size_t front_items = 0;
-  for (const auto& mb : mbs) front_items = std::max(front_items, (size_t)mb.count);
-  {
-    size_t wmax = 0, emax = 0, nmax = 0, pmax = 0, fmax = 0, hmax = 0;
-    for (const auto& mb : mbs) {
-      const long n = mb.nd;
-      const size_t k = (size_t)mb.count;
-      wmax = std::max(wmax, k * (size_t)n * 8);
-      emax = std::max(emax, k * highpass_ext_doubles(n));
-      nmax = std::max(nmax, k * (size_t)n);
-      pmax = std::max(pmax, k * (size_t)(n + 2 * g.t_pad));
-      fmax = std::max(fmax, k * (size_t)((n + 2 * g.t_pad) / 160 + 8));
-      // every chunk carries 2 * t_pad samples of context beyond its share of the clip
-      hmax = std::max(hmax, k * (size_t)E * (size_t)((n + 2 * g.t_pad + (cut_count(n, g) + 1) * (2 * g.t_pad + 640)) / 320 + 8));
-    }
-    for (auto& f : fr) {
-      f.wav = A.alloc<char>(wmax);
-      f.ext = A.alloc<double>(emax);
-      f.a64 = A.alloc<double>(nmax);
-      f.a32 = A.alloc<float>(nmax);
-      f.apad = A.alloc<float>(pmax);
-      f.f0 = A.alloc<float>(fmax);
-      f.coarse = A.alloc<int>(fmax);
-      f.feats = A.alloc<float>(hmax);
-      f.feats_cap = hmax;
-      f.ns = A.alloc<int>(front_items);
-    }
+  for (auto& f : fr) {
+    f.wav = L.alloc<char>(wmax);
+    f.ext = L.alloc<double>(emax);
+    f.a64 = L.alloc<double>(nmax);
+    f.a32 = L.alloc<float>(nmax);
+    f.apad = L.alloc<float>(pmax);
+    f.f0 = L.alloc<float>(fmax);
+    f.coarse = L.alloc<int>(fmax);
+    f.feats = L.alloc<float>(hmax);
+    f.feats_cap = hmax;
+    f.ns = L.alloc<int>(front_items);
   }
   // resample_sr (pipeline.py:453-454): librosa.resample(audio_opt, orig_sr=tgt_sr, target_sr=resample_sr) ahead of the peak
   // normalisation -- hard-wired off by rvc_infer (infer.py:144), reachable through VC.pipeline
   const bool resamp = p.resample_sr >= 16000 && p.resample_sr != M.cfg.sr;
   ResampleFilter rs_filter;
-  if (resamp) rs_filter = make_resample_filter(A, M.cfg.sr, p.resample_sr, s);
+  if (resamp) rs_filter = make_resample_filter(L, M.cfg.sr, p.resample_sr, s);
   const size_t work_mark = A.mark();
 
-  float t_hp = 0, t_f0 = 0, t_hub = 0, t_idx = 0, t_syn[3] = {0, 0, 0}, t_post = 0, t_wait_hub = 0, t_wait_f0 = 0;
-  struct Span {
-    int a, b;
-    float* acc;
-  };
-  std::vector<Span> spans;
+  float &t_hp = st.t_hp, &t_idx = st.t_idx, &t_post = st.t_post, &t_wait_hub = st.t_wait_hub, &t_wait_f0 = st.t_wait_f0;
+  std::vector<ConvertState::Span>& spans = st.spans;
   // RVCX_FRONT_DELAY (experiments): 0 (default) = the next micro-batch's front end starts as soon as its buffers are
   // free, 1 = when the main stream reaches this micro-batch's synthesizer, 2 = when it reaches the NSF decoder.
   // Measured on C3 (64 x 30 s): 1036 / 1030 / 1031 x -- at B = 8 HuBERT and the F0 model are throughput-bound like the
@@ -904,7 +996,10 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   };
 
   // ---- F0 of one micro-batch on `sf` out of its own arena (pipeline.py:362-380: once per utterance)
-  std::vector<int> f0_ev0(mbs.size(), -1), f0_ev1(mbs.size(), -1);
+  st.n_mbs = mbs.size();
+  std::vector<int>&f0_ev0 = st.f0_ev0, &f0_ev1 = st.f0_ev1;
+  f0_ev0.assign(mbs.size(), -1);
+  f0_ev1.assign(mbs.size(), -1);
   auto enqueue_f0 = [&](int k, const std::function<void()>* mid) {
     const MB& mb = mbs[k];
     Front& f = fr[k & 1];
@@ -940,8 +1035,8 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
     if (sf != s) RVCX_HIP(hipEventRecord(c.ev_join, sf));
   };
 
-  const int e_begin = clk.mark(s);
-  std::vector<std::array<hipEvent_t, 4>> syn_ev;   // synth_forward's own stage events (resolved after the final sync)
+  st.e_begin = clk.mark(s);
+  std::vector<std::array<hipEvent_t, 4>>& syn_ev = st.syn_ev;   // synth_forward's own stage events (resolved by convert_finish)
 
   front(0);
   const bool use_protect = p.protect < 0.5f;
@@ -1033,7 +1128,9 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   // HuBERT k queues behind decoder k - 1's last aux[0] branch, so the HuBERT / decoder overlap of rounds 2-3 (a stream of
   // its own) is gone -- traded, with a measured net gain, for not paying the fifth stream's shared hardware queue (api.hip;
   // DESIGN "Four streams, not five").  What still overlaps: HuBERT k beside the F0 model of k (front stream).
-  std::vector<int> hub_ev0(mbs.size(), -1), hub_ev1(mbs.size(), -1);
+  std::vector<int>&hub_ev0 = st.hub_ev0, &hub_ev1 = st.hub_ev1;
+  hub_ev0.assign(mbs.size(), -1);
+  hub_ev1.assign(mbs.size(), -1);
   auto enqueue_hubert = [&](int k) {
     const MB& mb = mbs[k];
     Plan& P = plans[k & 1];
@@ -1087,13 +1184,18 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
   // C2 on one box, HuBERT enqueued behind level 2 / 3 / 4 / the intermediate layers / the whole U-Net: 1041-1055 /
   // 1039-1050 / 1044-1064 / 1058-1072 / 1078-1081x; batched calls do not care (C3 1290 / 1295x with / without the wait).
   // Other F0 methods have no such hook: HuBERT is enqueued behind them and does not wait.
-  int mid_mark = -1;
+  int& mid_mark = st.mid_mark;
   // Round 6: the wait is for front ends that run EXPOSED and latency-bound -- a single utterance, or the first micro-batch
   // of a call when it is small (B = 2 / 3 / 4 in one call: 1360 / 1433 / 1474x with the wait, 1311 / 1408 / 1453 without;
   // B = 8: level).  A front end that runs beside the previous micro-batch's decoder is a throughput-type neighbour and HuBERT
   // beside its U-Net is free: C3 1468 - 1471 -> 1486 - 1491x without the wait (tools/sweep_c3_knobs.sh,
   // tools/sweep_gate_small_batches.sh).  RVCX_HUBERT_GATE: 0 never, 1 always, unset = this rule.
   static const int hub_gate_env = getenv("RVCX_HUBERT_GATE") ? atoi(getenv("RVCX_HUBERT_GATE")) : -1;
+  // A ticket's first front end that runs beside the previous ticket's decoder is the "throughput-type neighbour" case even
+  // when it holds a single utterance.  RVCX_TICKET_GATE: 1 = such a front end keeps the wait of an exposed one, 0 = it runs
+  // like micro-batch k >= 1 of a call (no wait); the default is the measured one (LABNOTES "Tickets").  Scheduling only.
+  static const int ticket_gate_env = getenv("RVCX_TICKET_GATE") ? atoi(getenv("RVCX_TICKET_GATE")) : 1;
+  const bool beside = ticket && ticket->beside_predecessor;
   auto enqueue_models = [&](int k) {
     bool hub_done = false, from_hook = true;
     bool cutting = false;
@@ -1103,7 +1205,8 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       if (hub_done || (cutting && from_hook)) return;
       hub_done = true;
       if (k == 0) mid_mark = clk.mark(sf);
-      const bool hub_gate = hub_gate_env < 0 ? (mbs[k].count <= 1 || (k == 0 && mbs[k].count < 8)) : hub_gate_env != 0;
+      bool hub_gate = hub_gate_env < 0 ? (mbs[k].count <= 1 || (k == 0 && mbs[k].count < 8)) : hub_gate_env != 0;
+      if (hub_gate_env < 0 && k == 0 && beside && !ticket_gate_env) hub_gate = false;
       if (hub_gate && from_hook && sh != sf) {
         RVCX_HIP(hipEventRecord(c.ev_hub, sf));
         RVCX_HIP(hipStreamWaitEvent(sh, c.ev_hub, 0));
@@ -1290,11 +1393,23 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       RVCX_HIP(hipEventRecord(c.ev_io, s));
       RVCX_HIP(hipStreamWaitEvent(sio, c.ev_io, 0));
     }
+    auto copy_out = [&](void* dst, const void* src, size_t bytes) {
+      if (ticket && !host_visible_to_device(dst)) {       // plain host memory: through the slot's pinned staging
+        Ctx::TicketSlot& sl = c.slot[ticket->slot];
+        const size_t off = stage_off;
+        stage_off += (bytes + 255) & ~size_t(255);
+        RVCX_CHECK(stage_off <= sl.stage_cap, "internal: ticket staging smaller than the outputs");
+        RVCX_HIP(hipMemcpyAsync(sl.stage + off, src, bytes, hipMemcpyDeviceToHost, sio));
+        ticket->staged.push_back({dst, off, bytes});
+      } else {
+        RVCX_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, sio));
+      }
+    };
     for (int b = 0; b < Bm; ++b) {
       Utt& u = utts[order[mb.first + b]];
       UttIO& io = ios[u.io];
-      RVCX_HIP(hipMemcpyAsync(io.out, u.pcm, (size_t)u.out_n * sizeof(short), hipMemcpyDefault, sio));
-      if (io.out_f32) RVCX_HIP(hipMemcpyAsync(io.out_f32, u.outf, (size_t)u.out_n * sizeof(float), hipMemcpyDefault, sio));
+      copy_out(io.out, u.pcm, (size_t)u.out_n * sizeof(short));
+      if (io.out_f32) copy_out(io.out_f32, u.outf, (size_t)u.out_n * sizeof(float));
       io.out_n = u.out_n;
     }
     if (sf != s) RVCX_HIP(hipEventRecord(c.ev_done[k & 1], s));
@@ -1307,42 +1422,47 @@ void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& ios, const rvcx_par
       ht("hubert+f0", k + 1);
     }
   }
-  const int e_end = clk.mark(s);
-  // the device error word travels with the call's own synchronisation (Ctx::snapshot_dev_err): every kernel that can set it
-  // has been joined into the main stream by now (F0 and HuBERT streams through ev_join / ev_hubdone, the branch streams
-  // at each stage's end)
-  c.snapshot_dev_err(s);
-  RVCX_HIP(hipStreamSynchronize(s));
-  if (sf != s) RVCX_HIP(hipStreamSynchronize(sf));
-  if (sio != s) RVCX_HIP(hipStreamSynchronize(sio));
-  if (stage_ms) {
-    for (const auto& sp : spans) *sp.acc += clk.between(sp.a, sp.b);
-    for (size_t k = 0; k < mbs.size(); ++k) t_f0 += clk.between(f0_ev0[k], f0_ev1[k]);
-    for (size_t k = 0; k < mbs.size(); ++k) t_hub += clk.between(hub_ev0[k], hub_ev1[k]);
-    for (auto& ev : syn_ev) {
-      for (int i = 0; i < 3; ++i) {
-        float t = 0.f;
-        RVCX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
-        t_syn[i] += t;
-      }
-      for (auto& e : ev) (void)hipEventDestroy(e);
-    }
-    if (getenv("RVCX_HOST_TRACE") && !mbs.empty())     // device-side times of the first micro-batch's front end, from its first event
-      fprintf(stderr, "[front] F0 model %.2f .. %.2f ms (shallow U-Net levels enqueued and done by %.2f), HuBERT %.2f .. %.2f ms\n",
-              clk.between(0, f0_ev0[0]), clk.between(0, f0_ev1[0]), clk.between(0, mid_mark), clk.between(0, hub_ev0[0]),
-              clk.between(0, hub_ev1[0]));
-    if (getenv("RVCX_HOST_TRACE"))
-      fprintf(stderr, "[wait] main stream waited %.1f ms for HuBERT / front sets and %.1f ms for F0\n", t_wait_hub, t_wait_f0);
-    stage_ms[0] = t_hp;
-    stage_ms[1] = t_f0;     // on the front stream, overlapped with HuBERT / the previous micro-batch's decoder
-    stage_ms[2] = t_hub;    // on HuBERT's stream, beside the F0 model and (k >= 1) the previous micro-batch's decoder
-    stage_ms[3] = t_idx;
-    stage_ms[4] = t_syn[0];
-    stage_ms[5] = t_syn[1];
-    stage_ms[6] = t_syn[2];
-    stage_ms[7] = t_post;
-    stage_ms[8] = clk.between(e_begin, e_end);
+  st.e_end = clk.mark(s);
+  st.last_mbs = c.last_mbs;
+  st.last_cuts = c.last_cuts;
+  if (ticket) {
+    // the ticket's error word and completion event travel behind its last copy on the main stream; every kernel that can
+    // set the word has been joined into the main stream by now
+    Ctx::TicketSlot& sl = c.slot[ticket->slot];
+    RVCX_HIP(hipMemcpyAsync(sl.err_host, sl.err, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (ticket->ev_done) RVCX_HIP(hipEventRecord(ticket->ev_done, s));
   }
+  return stp;
+}
+
+void convert_finish(Ctx& c, ConvertState& st, float* stage_ms) {
+  (void)c;
+  StageClock& clk = st.clk;
+  if (!clk.on || !stage_ms) return;
+  for (const auto& sp : st.spans) *sp.acc += clk.between(sp.a, sp.b);
+  for (size_t k = 0; k < st.n_mbs; ++k) st.t_f0 += clk.between(st.f0_ev0[k], st.f0_ev1[k]);
+  for (size_t k = 0; k < st.n_mbs; ++k) st.t_hub += clk.between(st.hub_ev0[k], st.hub_ev1[k]);
+  for (auto& ev : st.syn_ev)
+    for (int i = 0; i < 3; ++i) {
+      float t = 0.f;
+      RVCX_HIP(hipEventElapsedTime(&t, ev[i], ev[i + 1]));
+      st.t_syn[i] += t;
+    }
+  if (getenv("RVCX_HOST_TRACE") && st.n_mbs > 0)     // device-side times of the first micro-batch's front end, from its first event
+    fprintf(stderr, "[front] F0 model %.2f .. %.2f ms (shallow U-Net levels enqueued and done by %.2f), HuBERT %.2f .. %.2f ms\n",
+            clk.between(0, st.f0_ev0[0]), clk.between(0, st.f0_ev1[0]), clk.between(0, st.mid_mark), clk.between(0, st.hub_ev0[0]),
+            clk.between(0, st.hub_ev1[0]));
+  if (getenv("RVCX_HOST_TRACE"))
+    fprintf(stderr, "[wait] main stream waited %.1f ms for HuBERT / front sets and %.1f ms for F0\n", st.t_wait_hub, st.t_wait_f0);
+  stage_ms[0] = st.t_hp;
+  stage_ms[1] = st.t_f0;     // on the front stream, overlapped with HuBERT / the previous micro-batch's decoder
+  stage_ms[2] = st.t_hub;    // on HuBERT's stream, beside the F0 model and (k >= 1) the previous micro-batch's decoder
+  stage_ms[3] = st.t_idx;
+  stage_ms[4] = st.t_syn[0];
+  stage_ms[5] = st.t_syn[1];
+  stage_ms[6] = st.t_syn[2];
+  stage_ms[7] = st.t_post;
+  stage_ms[8] = clk.between(st.e_begin, st.e_end);
 }
 
 }  // namespace rvcx

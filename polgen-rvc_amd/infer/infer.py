@@ -244,3 +244,24 @@ def rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method,
                             hop_length, f0_file=None, f0_min=f0_min, f0_max=f0_max)
     # infer.py:153: sf.write(output_path, audio_opt, tgt_sr, format="WAV") -- a WAV whatever the extension says
     write_output(output_path, audio_opt, tgt_sr)
+
+
+def rvc_infer_many(index_path, index_rate, input_paths, output_paths, pitch, f0_method, cpt, version, net_g,
+                   filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
+                   f0_max=1100):
+    """``rvc_infer`` over lists of paths (the reference lists batch conversion as not done, TODO.md:11) through
+    ``VC.pipeline_stream``: two conversions are in flight while the next file is decoded, and every output file holds
+    the bytes ``rvc_infer`` writes for it.  A file that is not at 16 kHz is resampled on the GPU by ``load_audio``; the
+    resampler is the one entry point of the context that does not complete the conversions in flight first (it works in
+    a buffer of its own on the front stream, beside their synthesizer)."""
+    from .audio import write_output
+    input_paths, output_paths = list(input_paths), list(output_paths)
+    if len(input_paths) != len(output_paths):
+        raise ValueError("rvc_infer_many: one output path per input path")
+    pitch_guidance = cpt.get("f0", 1)
+    clips = (load_audio(path, 16000) for path in input_paths)          # lazy: decoded as the stream asks for them
+    results = vc.pipeline_stream(hubert_model, net_g, 0, clips, None, pitch, f0_method, index_path, index_rate,
+                                 pitch_guidance, filter_radius, tgt_sr, 0, volume_envelope, version, protect,
+                                 hop_length, f0_file=None, f0_min=f0_min, f0_max=f0_max)
+    for out_path, audio_opt in zip(output_paths, results):
+        write_output(out_path, audio_opt, tgt_sr)

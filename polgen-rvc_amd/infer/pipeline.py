@@ -75,6 +75,27 @@ class IndexHandle:
         self.ctx, self.key, self.ntotal, self.d = ctx, key, ntotal, dim
 
 
+class PipelineHandle:
+    """A VC.pipeline call in flight (VC.pipeline_async): ``result()`` is what ``pipeline`` returns, ``done()`` polls."""
+
+    def __init__(self, ticket, return_f32):
+        self._ticket, self._f32 = ticket, return_f32
+        self._res = None
+
+    def done(self) -> bool:
+        return self._res is not None or self._ticket.done()
+
+    def result(self):
+        if self._res is None:
+            res = self._ticket.wait()
+            self._res = (res[0][0], res[1][0]) if self._f32 else res[0]
+        return self._res
+
+    @property
+    def lead_ms(self) -> float:
+        return self._ticket.lead_ms
+
+
 class VC:
     def __init__(self, tgt_sr, config):
         # rvc/infer/pipeline.py:66-84
@@ -294,7 +315,7 @@ class VC:
     @_with_ctx_lock
     def pipeline_batch(self, model, net_g, sid, audios, pitch, f0_method, file_index, index_rate, pitch_guidance,
                        tgt_sr, resample_sr, volume_envelope, version, protect, f0_file=None, f0_min=50, f0_max=1100,
-                       *, noise=None, return_f32=False, _single=False, hop_length=128, crepe_dither=None):
+                       *, noise=None, return_f32=False, _single=False, hop_length=128, crepe_dither=None, _submit=False):
         """VC.pipeline over a list of utterances in one call (the reference lists batch conversion as not
         done, TODO.md:11): equal-length clips run through the networks together."""
         self._check_method(f0_method)
@@ -326,9 +347,45 @@ class VC:
             clips = [c.astype(np.float64) for c in clips]
         if f0_method == "mangio-crepe" and crepe_dither is None:     # one value per frame of each PADDED clip, drawn in order
             crepe_dither = [_crepe_dither(ctx.crepe_frames(c.shape[0] + 2 * self.t_pad, p.hop_length)) for c in clips]
-        res = ctx.convert_batch(net_g.model_id, clips, p, noise, want_f32=return_f32,
-                                inp_f0=None if inp_f0 is None else [inp_f0] * len(clips),
-                                crepe_dither=crepe_dither if f0_method == "mangio-crepe" else None)
+        convert = ctx.convert_submit if _submit else ctx.convert_batch
+        res = convert(net_g.model_id, clips, p, noise, want_f32=return_f32,
+                      inp_f0=None if inp_f0 is None else [inp_f0] * len(clips),
+                      crepe_dither=crepe_dither if f0_method == "mangio-crepe" else None)
+        if _submit:
+            return res          # the Ticket: every check, the index, the f0 file and the dither were dealt with above
         if _single:
             return (res[0][0], res[1][0]) if return_f32 else res[0]
         return res
+
+    def pipeline_async(self, model, net_g, sid, audio, input_audio_path, pitch, f0_method, file_index, index_rate,
+                       pitch_guidance, filter_radius, tgt_sr, resample_sr, volume_envelope, version, protect,
+                       hop_length, f0_file, f0_min=50, f0_max=1100, *, noise=None, return_f32=False, crepe_dither=None):
+        """``pipeline`` without the wait: the conversion is enqueued (argument checks, index loading, f0-file parsing and
+        the crepe dither draw happen here and raise here) and a handle comes back; ``handle.result()`` is what
+        ``pipeline`` returns.  Two calls may be in flight per context: the front end of the second runs while the first is
+        in its synthesizer.  Making another index resident while a call is in flight completes that call first."""
+        if noise is None:
+            noise = getattr(self, "parity_noise", None)
+        ticket = self.pipeline_batch(model, net_g, sid, [audio], pitch, f0_method, file_index, index_rate,
+                                     pitch_guidance, tgt_sr, resample_sr, volume_envelope, version, protect, f0_file,
+                                     f0_min, f0_max, noise=None if noise is None else [noise],
+                                     return_f32=return_f32, hop_length=hop_length,
+                                     crepe_dither=None if crepe_dither is None else [crepe_dither], _submit=True)
+        return PipelineHandle(ticket, return_f32)
+
+    def pipeline_stream(self, model, net_g, sid, audios, input_audio_path, pitch, f0_method, file_index, index_rate,
+                        pitch_guidance, filter_radius, tgt_sr, resample_sr, volume_envelope, version, protect,
+                        hop_length, f0_file, f0_min=50, f0_max=1100, *, return_f32=False):
+        """A generator over an iterable of clips: ``pipeline`` of each, in input order, with two conversions in flight
+        (clip n + 2 is taken from the iterable -- decoded, for a lazy one -- while n and n + 1 are on the device).  The
+        form a folder conversion or a request queue uses."""
+        pending = []
+        for audio in audios:
+            pending.append(self.pipeline_async(model, net_g, sid, audio, input_audio_path, pitch, f0_method, file_index,
+                                               index_rate, pitch_guidance, filter_radius, tgt_sr, resample_sr,
+                                               volume_envelope, version, protect, hop_length, f0_file, f0_min, f0_max,
+                                               return_f32=return_f32))
+            if len(pending) > 2:        # the third submit completed the oldest conversion inside the library
+                yield pending.pop(0).result()
+        while pending:
+            yield pending.pop(0).result()

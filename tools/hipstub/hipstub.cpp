@@ -10,7 +10,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
+#include <chrono>
 #include <map>
+#include <thread>
 #include <mutex>
 
 namespace {
@@ -20,7 +23,19 @@ constexpr size_t kBig = (size_t)256 << 20;
 long g_launches = 0, g_live_events = 0, g_live_streams = 0;
 struct Obj {
   int kind;
+  std::atomic<long long> ready_ns{0};   // events: the moment the "device" reaches the record
 };
+// A recorded event completes a little later, as on a device that is still working: hipEventQuery says "not ready" and
+// hipEventSynchronize really blocks until then, so that code which waits without its lock is contended under the sanitizers.
+constexpr long long kEventDelayNs = 300000;
+std::atomic<long long> g_busy_until_ns{0};
+long long now_ns() {
+  return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+void sleep_until_ns(long long t) {
+  const long long d = t - now_ns();
+  if (d > 0) std::this_thread::sleep_for(std::chrono::nanoseconds(d));
+}
 }  // namespace
 
 extern "C" {
@@ -50,7 +65,10 @@ hipError_t hipDeviceGetStreamPriorityRange(int* lo, int* hi) {
   *hi = -1;
   return hipSuccess;
 }
-hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
+hipError_t hipDeviceSynchronize(void) {
+  sleep_until_ns(g_busy_until_ns.load());
+  return hipSuccess;
+}
 hipError_t hipGetLastError(void) { return hipSuccess; }
 const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "success" : "hipstub error"; }
 hipError_t hipMemGetInfo(size_t* f, size_t* t) {
@@ -125,7 +143,10 @@ hipError_t hipStreamDestroy(hipStream_t s) {
   --g_live_streams;
   return hipSuccess;
 }
-hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
+hipError_t hipStreamSynchronize(hipStream_t) {
+  sleep_until_ns(g_busy_until_ns.load());
+  return hipSuccess;
+}
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) {
   *e = reinterpret_cast<hipEvent_t>(new Obj{2});
@@ -138,8 +159,21 @@ hipError_t hipEventDestroy(hipEvent_t e) {
   --g_live_events;
   return hipSuccess;
 }
-hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventRecord(hipEvent_t e, hipStream_t) {
+  const long long t = now_ns() + kEventDelayNs;
+  reinterpret_cast<Obj*>(e)->ready_ns.store(t);
+  long long cur = g_busy_until_ns.load();
+  while (cur < t && !g_busy_until_ns.compare_exchange_weak(cur, t)) {
+  }
+  return hipSuccess;
+}
+hipError_t hipEventSynchronize(hipEvent_t e) {
+  sleep_until_ns(reinterpret_cast<Obj*>(e)->ready_ns.load());
+  return hipSuccess;
+}
+hipError_t hipEventQuery(hipEvent_t e) {
+  return now_ns() >= reinterpret_cast<Obj*>(e)->ready_ns.load() ? hipSuccess : hipErrorNotReady;
+}
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) {
   *ms = 0.001f;
   return hipSuccess;
