@@ -199,6 +199,18 @@ int rvcx_synth_infer_taps(rvcx_ctx*, int model_id, int B, int T, const int32_t* 
                           const float* phone_hd, const int32_t* pitch_hd, const float* pitchf_hd,
                           const int32_t* sid, const float* z_noise_hd, const float* src_noise_hd,
                           uint64_t seed, float* out_hd, float* stats_hd, float* zflow_hd);
+/* Synthesizer.infer(..., rate) -- synthesizers.py:170-181 -- with the head given in FRAMES: the TextEncoder and the z_p draw
+ * run over all T frames, then z_p, the mask and nsff0 are sliced to [skip_head:] and the four coupling layers, the harmonic
+ * source (whose phase accumulation starts at the slice) and the whole decoder run at T - skip_head frames.  This is not the
+ * decoder window above: the flow and the source see the slice, not the whole, and the result differs from the tail of a
+ * full evaluation.  The reference computes head = int(T * (1.0 - rate)) with rate a float32 tensor (the Python mirror's
+ * head_from_rate restates it).  z_noise (B, inter, T); src_noise and out (B, (T - skip_head) * upp); zflow optional
+ * (B, inter, T - skip_head).  Errors: skip_head outside [0, T); lens that are not all T together with skip_head > 0.
+ * skip_head = 0 takes the launches of the plain call and returns its bits. */
+int rvcx_synth_infer_head(rvcx_ctx*, int model_id, int B, int T, const int32_t* lens, const float* phone_hd,
+                          const int32_t* pitch_hd, const float* pitchf_hd, const int32_t* sid,
+                          const float* z_noise_hd, const float* src_noise_hd, uint64_t seed, int skip_head,
+                          float* out_hd, float* zflow_hd);
 int rvcx_synth_upp(rvcx_ctx*, int model_id);
 /* index.search(k=8) + weighted blend -- rvc/infer/pipeline.py:239-250.
  * feats (T, dim) in/out; ids (T,8) int64 and dist (T,8) optional. */
@@ -349,6 +361,62 @@ int rvcx_vc(rvcx_ctx*, int model_id, const float* audio0_hd, int64_t n, const in
             const float* pitchf_hd, int n_pitch, int sid, float index_rate, float protect,
             const float* z_noise_hd, const float* src_noise_hd, uint64_t seed, float* out_hd, int64_t* out_n);
 int rvcx_vc_frames(rvcx_ctx*, int64_t n);
+
+/* ---- live streams ---------------------------------------------------------------------------------------------------
+ * A session is S lock-step streams of one geometry on one voice model: every step takes one block of 16 kHz mono float32
+ * per stream and returns the converted block at the model's rate before the next one arrives.  All lengths are 10 ms frames:
+ * block Fb, context Fc, cross-fade Fx, search Fs.  Per stream the session owns (device memory of its own, not arena scratch)
+ * a ring of N = Fc + Fx + Fs + Fb frames (zeros at open), the SOLA carry (Fx * upp samples, zeros) and a step counter.
+ *
+ * One step: (1) every ring moves left by one block and the new block is appended; (2) the F0 model p->f0_method names
+ * ("rmvpe" / "rmvpe+" or "fcpe") runs on the whole ring with B = S, then the pitch shift and coarse quantisation of VC.get_f0
+ * (pipeline.py:183-201) per stream with that stream's `pitch`; (3) what VC.vc does (pipeline.py:203-287) with B = S: HuBERT
+ * (v1 / v2 by the model's input_dim), the retrieval blend when an index is resident and p->index_rate != 0, x2 upsample and
+ * protect mix, T = min(N, 2 * HuBERT frames); (4) the synthesizer with skip_head = T - (Fb + Fx + Fs) and per-stream sid: only
+ * the tail is synthesized; (5) SOLA per stream on the device (below), then the block is copied out.  The chosen offset never
+ * travels to the host inside a step unless `offsets` asks for it.
+ *
+ * p_len clamp: with HuBERT-base 2 * frames = N - 1, so T = N - 1 and the newest frame of the ring has no synthesized
+ * counterpart -- one frame (10 ms) of added latency, the clamp of pipeline.py:257-262.
+ *
+ * Deliberately absent, because they are whole-clip operations of VC.pipeline (pipeline.py:329, 450-461): the 48 Hz zero-phase
+ * high-pass, the volume envelope, resample_sr and the peak normalisation.  Neither is there resampling: input is 16 kHz mono
+ * float32; callers resample with rvcx_resample_f64, which runs beside other work.
+ *
+ * Noise.  noise_hd[s] (parity): z_noise (inter * T) then src_noise ((Fb + Fx + Fs) * upp) for this step.  NULL: stream s draws
+ * from Philox(p->seed + s) at counter offsets that no two steps share.  A reset zeroes ring, carry and step counter: a reset
+ * session replays a fresh one bit for bit.  Every stream's output equals that of the same stream stepped alone in a session
+ * of its own, bit for bit.
+ *
+ * Rules.  Fb, Fx >= 1, Fs >= 0, n_streams >= 1, and Fb + Fx + Fs <= T, else open fails.  "mangio-crepe" is refused at open (its
+ * Viterbi pass and host dither have no place in a per-block loop).  Open fails when a resident index's width differs from the
+ * model's input_dim, and when the activation budget cannot hold one step at this S (the message names the largest S that
+ * fits).  A step completes the tickets in flight first, like every other entry point, and holds the context's mutex.  A step
+ * on a session whose voice model was unloaded returns -1 with a message.  rvcx_destroy closes open sessions. */
+typedef struct {
+  int32_t n_streams, block_frames, context_frames, crossfade_frames, search_frames; /* 10 ms frames */
+} rvcx_stream_cfg;
+/* sid (S) speaker ids, pitch (S) semitones; of *p the fields f0_method, f0_min, f0_max, index_rate, protect and seed are used */
+int rvcx_stream_open(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_params* p, const int32_t* sid,
+                     const float* pitch, int* stream_id);
+/* block16k_hd: S pointers to Fb * 160 samples; out_hd: S pointers to Fb * upp samples; pre_sola_hd (optional): S pointers to
+ * (Fb + Fx + Fs) * upp samples, the synthesized tail before SOLA; offsets (optional, host): the S chosen SOLA offsets */
+int rvcx_stream_step(rvcx_ctx*, int stream_id, const float* const* block16k_hd, const float* const* noise_hd,
+                     float* const* out_hd, float* const* pre_sola_hd, int32_t* offsets);
+int rvcx_stream_reset(rvcx_ctx*, int stream_id);
+int rvcx_stream_close(rvcx_ctx*, int stream_id);
+int64_t rvcx_stream_out_len(rvcx_ctx*, int stream_id);   /* Fb * upp */
+int64_t rvcx_stream_noise_len(rvcx_ctx*, int stream_id); /* inter * T + (Fb + Fx + Fs) * upp per stream and step */
+int rvcx_stream_frames(rvcx_ctx*, int stream_id);        /* T, the frames the TextEncoder sees per step */
+/* SOLA (synchronised overlap-add) of one synthesized tail y (Lb + Lx + Ls samples) against the carry b_in (Lx samples):
+ *   for d = 0 .. Ls inclusive: nom[d] = sum_{i<Lx} y[d+i] b[i], den[d] = sqrt(sum_{i<Lx} y[d+i]^2 + 1e-8);
+ *   d* = the FIRST index of max(nom / den);  out[i] = y[d*+i] (i < Lb), cross-faded with the carry over its first
+ *   min(Lx, Lb) samples: out[i] = y[d*+i] fin[i] + b[i] (1 - fin[i]), fin[i] = sin^2(pi/2 i / (Lx - 1));
+ *   new carry b_out[i] = y[d* + Lb + i].
+ * float32 on the device, one wave per offset, every energy sum formed directly (silence ties exactly, no drift).
+ * scores (optional): the Ls + 1 values nom / den.  Pointers may be host or device; b_out may be b_in. */
+int rvcx_op_sola(rvcx_ctx*, const float* y_hd, const float* b_in_hd, int Lb, int Lx, int Ls, float* out_hd,
+                 float* b_out_hd, int32_t* offset, float* scores_hd);
 
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last

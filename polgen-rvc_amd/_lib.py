@@ -71,6 +71,37 @@ class UttExtra(C.Structure):
 F0_RMVPE, F0_FCPE, F0_CREPE = 0, 1, 2        # rvcx_params.f0_method
 
 
+class StreamCfg(C.Structure):
+    """rvcx_stream_cfg: the geometry of a live-stream session in 10 ms frames"""
+    _fields_ = [("n_streams", C.c_int32), ("block_frames", C.c_int32), ("context_frames", C.c_int32),
+                ("crossfade_frames", C.c_int32), ("search_frames", C.c_int32)]
+
+
+def head_from_rate(T: int, rate) -> int:
+    """head = int(z_p.shape[2] * (1.0 - rate.item())) of Synthesizer.infer (synthesizers.py:177) for a float32 `rate` tensor:
+    .item() widens the float32 value to a Python float, the rest is float64.  T = 40: rate 0.3 -> 27 (not 28), 0.25 -> 30."""
+    return int(int(T) * (1.0 - float(np.float32(rate))))
+
+
+def sola_reference(y, b, Lb, Lx, Ls, offset=None):
+    """rvcx_op_sola restated in float64 numpy (the yardstick of its tests; no GPU): (out, new carry, offset, scores, mags)
+    with scores[d] = nom[d] / den[d] and mags[d] = sum |y[d+i] b[i]| / den[d] (what the rounding-error bound of a float32
+    evaluation scales with).  offset: apply this one instead of the first index of the maximum."""
+    y, b = np.asarray(y, np.float64), np.asarray(b, np.float64)
+    Lb, Lx, Ls = int(Lb), int(Lx), int(Ls)
+    assert y.shape == (Lb + Lx + Ls,) and b.shape == (Lx,)
+    win = np.lib.stride_tricks.sliding_window_view(y[:Ls + Lx], Lx)          # (Ls + 1, Lx)
+    den = np.sqrt((win * win).sum(1) + 1e-8)
+    scores = (win @ b) / den
+    mags = (np.abs(win) @ np.abs(b)) / den
+    d = int(np.argmax(scores)) if offset is None else int(offset)            # argmax: the first index of the maximum
+    out = y[d:d + Lb].copy()
+    k = min(Lx, Lb)
+    fin = np.sin(0.5 * np.pi * np.arange(Lx) / max(Lx - 1, 1)) ** 2
+    out[:k] = y[d:d + k] * fin[:k] + b[:k] * (1.0 - fin[:k])
+    return out, y[d + Lb:d + Lb + Lx].copy(), d, scores, mags
+
+
 _lib = None
 
 # every symbol include/rvcx.h declares (tests/test_abi.py checks the .so exports all of them)
@@ -87,6 +118,8 @@ SYMBOLS = [
     "rvcx_gru_fallbacks", "rvcx_gru_publish_probe", "rvcx_debug_inject", "rvcx_f0_file_track", "rvcx_op_gemm_tm", "rvcx_op_layernorm_tm",
     "rvcx_resample_len", "rvcx_resample_f64", "rvcx_resample_f64_kind", "rvcx_bench_gemm", "rvcx_device_info",
     "rvcx_convert_submit", "rvcx_convert_wait", "rvcx_convert_poll", "rvcx_convert_inflight", "rvcx_ticket_lead_ms",
+    "rvcx_synth_infer_head", "rvcx_op_sola", "rvcx_stream_open", "rvcx_stream_step", "rvcx_stream_reset", "rvcx_stream_close",
+    "rvcx_stream_out_len", "rvcx_stream_noise_len", "rvcx_stream_frames",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
 ]
 
@@ -131,6 +164,11 @@ def lib() -> C.CDLL:
         _lib.rvcx_convert_inflight.argtypes = [C.c_void_p]
         _lib.rvcx_ticket_lead_ms.argtypes = [C.c_void_p, C.c_int64]
         _lib.rvcx_ticket_lead_ms.restype = C.c_float
+        _lib.rvcx_stream_out_len.restype = C.c_int64
+        _lib.rvcx_stream_noise_len.restype = C.c_int64
+        _lib.rvcx_stream_out_len.argtypes = [C.c_void_p, C.c_int]
+        _lib.rvcx_stream_noise_len.argtypes = [C.c_void_p, C.c_int]
+        _lib.rvcx_stream_frames.argtypes = [C.c_void_p, C.c_int]
     return _lib
 
 
@@ -298,6 +336,63 @@ class Ticket:
                 lib().rvcx_convert_wait(self._ctx._h, self.id)
         except Exception:
             pass
+
+
+class StreamSession:
+    """S lock-step live streams (Context.stream_open).  step() takes one 16 kHz block per stream and returns the converted
+    blocks at the voice model's rate; the rolling context, the SOLA carry and the noise counters live on the device."""
+
+    def __init__(self, ctx, sid, cfg):
+        self._ctx, self.id, self.cfg = ctx, sid, cfg
+        self.n_streams = int(cfg.n_streams)
+        self.block_in = int(cfg.block_frames) * 160
+        self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))
+        self.noise_len = int(lib().rvcx_stream_noise_len(ctx._h, sid))
+        self.frames = int(lib().rvcx_stream_frames(ctx._h, sid))          # T of the TextEncoder
+        upp = self.block_out // int(cfg.block_frames)
+        self.tail_len = (int(cfg.block_frames) + int(cfg.crossfade_frames) + int(cfg.search_frames)) * upp
+        self.skip_head = self.frames - self.tail_len // upp
+
+    def step(self, blocks, noise=None, taps=False):
+        """blocks (S, Fb * 160) float32 -> (S, Fb * upp) float32.  noise (S, noise_len): parity noise of this step (z_noise
+        then src_noise per stream).  taps=True: (out, pre_sola (S, tail_len), offsets (S,))."""
+        if self.id is None:
+            raise RvcxError("StreamSession.step: the session is closed")
+        S = self.n_streams
+        x = f32(blocks)
+        if x.shape != (S, self.block_in):
+            raise RvcxError(f"StreamSession.step: blocks must be ({S}, {self.block_in}), got {x.shape}")
+        nz = None
+        if noise is not None:
+            nz = f32(noise)
+            if nz.shape != (S, self.noise_len):
+                raise RvcxError(f"StreamSession.step: noise must be ({S}, {self.noise_len})")
+        out = np.empty((S, self.block_out), np.float32)
+        pre = np.empty((S, self.tail_len), np.float32) if taps else None
+        offs = np.empty(S, np.int32) if taps else None
+
+        def table(a):
+            return None if a is None else (C.c_void_p * S)(*[a[i].ctypes.data for i in range(S)])
+        self._ctx._ck(lib().rvcx_stream_step(self._ctx._h, self.id, table(x), table(nz), table(out), table(pre),
+                                             _p(offs, C.c_int32)), "stream_step")
+        return (out, pre, offs) if taps else out
+
+    def reset(self):
+        """zero ring, carry and step counter: the session then replays a fresh one"""
+        self._ctx._ck(lib().rvcx_stream_reset(self._ctx._h, self.id), "stream_reset")
+
+    def close(self):
+        if self.id is not None and getattr(self._ctx, "_h", None):
+            sid, self.id = self.id, None
+            self._ctx._ck(lib().rvcx_stream_close(self._ctx._h, sid), "stream_close")
+        self.id = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
 
 
 class Context:
@@ -512,7 +607,10 @@ class Context:
         return int(lib().rvcx_synth_dec_rf(self._h, int(model_id)))
 
     def synth_infer(self, model_id, phone, pitch, pitchf, lens=None, sid=None, z_noise=None, src_noise=None,
-                    seed=0, taps=False, dec_skip=0):
+                    seed=0, taps=False, dec_skip=0, skip_head=None):
+        """skip_head (frames; Synthesizer.infer's `rate`, see head_from_rate): the flow, the source and the decoder run on
+        frames [skip_head:] only -- returns (out (B, (T - skip_head) * upp), zflow (B, inter, T - skip_head) or None without
+        z_noise); src_noise is (B, (T - skip_head) * upp)"""
         phone, pitchf = f32(phone), f32(pitchf)
         pitch = i32(pitch)
         B, T, _ = phone.shape
@@ -522,6 +620,19 @@ class Context:
         sid = i32(np.zeros(B) if sid is None else sid)
         zn = None if z_noise is None else f32(z_noise)
         sn = None if src_noise is None else f32(src_noise)
+        if skip_head is not None:
+            if taps or dec_skip:
+                raise RvcxError("synth_infer: dec_skip / taps and skip_head exclude each other")
+            head = int(skip_head)
+            Tk = max(T - head, 0)
+            if sn is not None and sn.size != B * Tk * upp:
+                raise RvcxError("synth_infer(skip_head=): src_noise must hold (T - skip_head) * upp samples per item")
+            out = np.empty((B, Tk * upp), np.float32)
+            zflow = None if zn is None else np.empty((B, zn.shape[1], Tk), np.float32)
+            self._ck(lib().rvcx_synth_infer_head(self._h, model_id, B, T, _p(lens, C.c_int32), _p(phone),
+                                                 _p(pitch, C.c_int32), _p(pitchf), _p(sid, C.c_int32), _p(zn), _p(sn),
+                                                 C.c_uint64(seed), head, _p(out), _p(zflow)), "synth_infer_head")
+            return out, zflow
         if taps:
             inter = (zn.shape[1] if zn is not None else None)
             if inter is None:
@@ -541,6 +652,30 @@ class Context:
                                         _p(pitch, C.c_int32), _p(pitchf), _p(sid, C.c_int32), _p(zn), _p(sn),
                                         C.c_uint64(seed), _p(out)), "synth_infer")
         return out
+
+    def sola(self, y, b, Lb, Lx, Ls, scores=False):
+        """rvcx_op_sola: (out (Lb,), new carry (Lx,), offset[, scores (Ls + 1,)])"""
+        y, b = f32(y), f32(b)
+        Lb, Lx, Ls = int(Lb), int(Lx), int(Ls)
+        if y.shape != (Lb + Lx + Ls,) or b.shape != (Lx,):
+            raise RvcxError("sola: y must hold Lb + Lx + Ls samples and b Lx")
+        out, nb = np.empty(Lb, np.float32), np.empty(Lx, np.float32)
+        off = C.c_int32(-1)
+        sc = np.empty(Ls + 1, np.float32) if scores else None
+        self._ck(lib().rvcx_op_sola(self._h, _p(y), _p(b), Lb, Lx, Ls, _p(out), _p(nb), C.byref(off), _p(sc)), "op_sola")
+        return (out, nb, int(off.value), sc) if scores else (out, nb, int(off.value))
+
+    def stream_open(self, model_id, params: "Params", sids, pitches, block_frames, context_frames, crossfade_frames,
+                    search_frames) -> "StreamSession":
+        """rvcx_stream_open: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms)"""
+        sid, pit = i32(np.atleast_1d(sids)), f32(np.atleast_1d(pitches))
+        if sid.ndim != 1 or sid.shape != pit.shape or sid.shape[0] < 1:
+            raise RvcxError("stream_open: one speaker id and one pitch per stream")
+        cfg = StreamCfg(int(sid.shape[0]), int(block_frames), int(context_frames), int(crossfade_frames), int(search_frames))
+        h = C.c_int(0)
+        self._ck(lib().rvcx_stream_open(self._h, int(model_id), C.byref(cfg), C.byref(params), _p(sid, C.c_int32), _p(pit),
+                                        C.byref(h)), "stream_open")
+        return StreamSession(self, int(h.value), cfg)
 
     def load_rmvpe(self, cfg_struct, state: dict):
         tbl, keep = make_table(state)

@@ -52,8 +52,37 @@ struct Ticket {
 };
 using TicketPtr = std::shared_ptr<Ticket>;
 
+// A live-stream session (rvcx_stream_open): S lock-step streams of one geometry on one voice model.  Ring, carry and block
+// staging are allocations of the session's own (the arena is scratch that other calls reset).  Ring and carry exist twice: a
+// step reads set `cur` and writes the other one, and the sets change places once the step has succeeded -- the body of a step
+// can then be repeated (range guard, BiGRU fallback) or fail without moving the session.
+struct StreamSession {
+  int model_id = 0;
+  std::weak_ptr<WeightRegion> region;      // expires when the voice model is unloaded (or replaced)
+  rvcx_stream_cfg cfg{};
+  rvcx_params p{};
+  std::vector<int> sid;
+  std::vector<float> pitch;
+  int S = 0, N = 0, Th = 0, T = 0, head = 0, upp = 0, inter = 0, E = 0;
+  long Lb = 0, Lx = 0, Ls = 0, Lk = 0;     // block, cross-fade, search and synthesized tail in output samples
+  float* ring[2] = {nullptr, nullptr};     // (S, N * 160) each
+  float* carry[2] = {nullptr, nullptr};    // (S, Lx) each
+  float* blocks = nullptr;                 // (S, Fb * 160): the step's new blocks, dense
+  int cur = 0;
+  uint64_t step = 0;
+  // RVCX_STREAM_FULL_SYNTH=1 (read at open; tools/bench_stream.py's A/B): the synthesizer runs with skip_head = 0 and SOLA takes
+  // the tail of the whole output -- what the step costs without the tail-only path (and NOT what the reference computes)
+  bool full_synth = false;
+  ~StreamSession() {
+    for (float* q : {ring[0], ring[1], carry[0], carry[1], blocks})
+      if (q) (void)hipFree(q);
+  }
+};
+
 struct rvcx_ctx {
   Ctx c;
+  std::unordered_map<int, std::unique_ptr<StreamSession>> sessions;
+  int next_session = 1;
   std::recursive_mutex mu;
   std::deque<TicketPtr> inflight;                          // submit order; at most two
   std::unordered_map<rvcx_ticket, TicketPtr> tickets;      // every ticket that has not been waited for
@@ -308,6 +337,7 @@ void rvcx_destroy(rvcx_ctx* ctx) {
     }
   }
   (void)hipDeviceSynchronize();
+  ctx->sessions.clear();       // open live-stream sessions close with the context
   delete ctx;
 }
 
@@ -999,7 +1029,8 @@ int rvcx_weights_adopt(rvcx_ctx* ctx) {
 
 static int synth_infer_impl(rvcx_ctx* ctx, int model_id, int B, int T, const int32_t* lens, const float* phone,
                             const int32_t* pitch, const float* pitchf, const int32_t* sid, const float* z_noise,
-                            const float* src_noise, uint64_t seed, float* out, float* stats, float* zflow, int dec_skip);
+                            const float* src_noise, uint64_t seed, float* out, float* stats, float* zflow, int dec_skip,
+                            int skip_head = 0);
 
 int rvcx_synth_infer(rvcx_ctx* ctx, int model_id, int B, int T, const int32_t* lens, const float* phone,
                      const int32_t* pitch, const float* pitchf, const int32_t* sid, const float* z_noise,
@@ -1031,13 +1062,27 @@ int rvcx_synth_infer_taps(rvcx_ctx* ctx, int model_id, int B, int T, const int32
                           zflow, 0);
 }
 
+int rvcx_synth_infer_head(rvcx_ctx* ctx, int model_id, int B, int T, const int32_t* lens, const float* phone,
+                          const int32_t* pitch, const float* pitchf, const int32_t* sid, const float* z_noise,
+                          const float* src_noise, uint64_t seed, int skip_head, float* out, float* zflow) {
+  CtxLock ctx_guard_ = lock_ctx(ctx);
+  return synth_infer_impl(ctx, model_id, B, T, lens, phone, pitch, pitchf, sid, z_noise, src_noise, seed, out, nullptr,
+                          zflow, 0, skip_head);
+}
+
 static int synth_infer_impl(rvcx_ctx* ctx, int model_id, int B, int T, const int32_t* lens, const float* phone,
                             const int32_t* pitch, const float* pitchf, const int32_t* sid, const float* z_noise,
-                            const float* src_noise, uint64_t seed, float* out, float* stats, float* zflow, int dec_skip) {
+                            const float* src_noise, uint64_t seed, float* out, float* stats, float* zflow, int dec_skip,
+                            int skip_head) {
   API_BEGIN(ctx)
   SynthModel& M = get_synth(*C, model_id);
   const int D = M.cfg.input_dim, inter = M.cfg.inter_channels;
-  const size_t Tupp = (size_t)T * M.upp;
+  if (skip_head < 0 || skip_head >= T) fail("synth_infer: skip_head outside [0, T)");
+  if (skip_head > 0 && lens)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] != T) fail("synth_infer: skip_head needs equal lengths (every item T frames)");
+  const int Tk = T - skip_head;                     // frames the source, the flow and the decoder see
+  const size_t Tupp = (size_t)Tk * M.upp;
   C->ensure_splitk(B);
   C->arena.reserve(synth_arena_bytes(M, B, T) + (size_t)B * T * D * 8 + (size_t)B * Tupp * 8 +
                    (size_t)B * 3 * inter * T * 4 + 4096);
@@ -1066,9 +1111,10 @@ static int synth_infer_impl(rvcx_ctx* ctx, int model_id, int B, int T, const int
   if (stats) io.stats_out = C->arena.alloc<float>((size_t)B * 2 * inter * T);
   if (zflow) io.z_out = C->arena.alloc<float>((size_t)B * inter * T);
   io.dec_skip = dec_skip;
+  io.skip_head = skip_head;
   synth_forward(*C, M, io, nullptr);
   if (stats) RVCX_HIP(hipMemcpyAsync(stats, io.stats_out, (size_t)B * 2 * inter * T * 4, hipMemcpyDefault, C->stream));
-  if (zflow) RVCX_HIP(hipMemcpyAsync(zflow, io.z_out, (size_t)B * inter * T * 4, hipMemcpyDefault, C->stream));
+  if (zflow) RVCX_HIP(hipMemcpyAsync(zflow, io.z_out, (size_t)B * inter * Tk * 4, hipMemcpyDefault, C->stream));
   RVCX_HIP(hipMemcpyAsync(out, dout, (size_t)B * Tupp * 4, hipMemcpyDefault, C->stream));
   RVCX_HIP(hipStreamSynchronize(C->stream));
   C->arena.reset();
@@ -2118,6 +2164,304 @@ int rvcx_vc(rvcx_ctx* ctx, int model_id, const float* audio0, int64_t n, const i
   C->arena.reset();
   API_END
 }
+
+// ------------------------------------------------------------------------------------------ live streams (rvcx.h)
+int rvcx_op_sola(rvcx_ctx* ctx, const float* y, const float* b_in, int Lb, int Lx, int Ls, float* out, float* b_out,
+                 int32_t* offset, float* scores) {
+  API_BEGIN(ctx)
+  if (!y || !b_in || !out || !b_out) fail("sola: null argument");
+  if (Lb < 1 || Lx < 1 || Ls < 0) fail("sola: Lb, Lx >= 1 and Ls >= 0");
+  const size_t Ly = (size_t)Lb + Lx + Ls;
+  C->arena.reserve((Ly + 2 * (size_t)Lx + Lb + Ls + 64) * 4 + (1 << 20));
+  C->arena.reset();
+  hipStream_t s = C->stream;
+  float* dy = any_to_dev(*C, y, Ly);
+  float* db = any_to_dev(*C, b_in, (size_t)Lx);
+  float* dout = C->arena.alloc<float>((size_t)Lb);
+  float* dbo = C->arena.alloc<float>((size_t)Lx);
+  float* dsc = C->arena.alloc<float>((size_t)Ls + 1);
+  int* doff = C->arena.alloc<int>(1);
+  launch_sola(dy, (long)Ly, db, dout, Lb, dbo, doff, dsc, 1, Lb, Lx, Ls, s);
+  RVCX_HIP(hipMemcpyAsync(out, dout, (size_t)Lb * 4, hipMemcpyDefault, s));
+  RVCX_HIP(hipMemcpyAsync(b_out, dbo, (size_t)Lx * 4, hipMemcpyDefault, s));
+  if (offset) RVCX_HIP(hipMemcpyAsync(offset, doff, 4, hipMemcpyDefault, s));
+  if (scores) RVCX_HIP(hipMemcpyAsync(scores, dsc, ((size_t)Ls + 1) * 4, hipMemcpyDefault, s));
+  RVCX_HIP(hipStreamSynchronize(s));
+  C->arena.reset();
+  API_END
+}
+
+// arena bytes of one step of S streams (the stages run one after the other on the main stream: the sum is an upper bound)
+static size_t stream_step_bytes(Ctx& c, const SynthModel& M, const rvcx_params& p, int S, int N, int Th, int T, long Lk,
+                                long Lb, long Ls) {
+  const long n = (long)N * 160;
+  const size_t E = (size_t)M.cfg.input_dim;
+  size_t need = f0_arena_bytes(c, p, S, n) + hubert_arena_bytes(*c.hubert, S, n) + synth_arena_bytes(M, S, T);
+  need += (size_t)S * ((size_t)(N + 8) * 32 + 2 * E * Th + E * T + (size_t)M.cfg.inter_channels * T + 2 * (size_t)Lk + Lb + Ls + 64) * 4;
+  need += (size_t)S * T * M.upp * 2 * 4;       // RVCX_STREAM_FULL_SYNTH: whole-length source noise and output
+  if (c.index) need += index_arena_bytes(*c.index, Th);
+  return need + ((size_t)64 << 20);
+}
+
+// the activation budget of a context (convert_micro_batch's rule, pipeline.hip): RVCX_ARENA_GB, else 100 GB but no more than
+// 70 % of what the device has free plus what the context's arenas already hold
+static size_t stream_budget(Ctx& c) {
+  size_t budget = (size_t)(getenv("RVCX_ARENA_GB") ? atoi(getenv("RVCX_ARENA_GB")) : 100) << 30;
+  if (getenv("RVCX_ARENA_GB")) return budget;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || total_b == 0) return budget;
+  const size_t mine = c.arena.capacity() + c.arena_f0.capacity() + c.arena_hub.capacity() + c.slot[0].arena.capacity() +
+                      c.slot[1].arena.capacity();
+  return std::max<size_t>(1, std::min(budget, (size_t)((double)(free_b + mine) * 0.7)));
+}
+
+static StreamSession& get_session(rvcx_ctx* h, int id) {
+  auto it = h->sessions.find(id);
+  if (it == h->sessions.end()) fail("stream: unknown session " + std::to_string(id));
+  return *it->second;
+}
+
+int rvcx_stream_open(rvcx_ctx* ctx, int model_id, const rvcx_stream_cfg* cfg, const rvcx_params* p, const int32_t* sid,
+                     const float* pitch, int* stream_id) {
+  API_BEGIN_ONCE(ctx)
+  if (!cfg || !p || !sid || !pitch || !stream_id) fail("stream_open: null argument");
+  SynthModel& M = get_synth(*C, model_id);
+  if (!C->hubert) fail("stream_open: hubert not loaded");
+  if (p->f0_method == RVCX_F0_CREPE)
+    fail("stream_open: mangio-crepe is not available to live streams (its Viterbi pass and host dither have no place in a "
+         "per-block loop); use rmvpe or fcpe");
+  check_f0_backend(*C, *p);
+  const int S = cfg->n_streams, Fb = cfg->block_frames, Fc = cfg->context_frames, Fx = cfg->crossfade_frames,
+            Fs = cfg->search_frames;
+  if (S < 1 || Fb < 1 || Fx < 1 || Fs < 0 || Fc < 0) fail("stream_open: n_streams, block, cross-fade >= 1 and context, search >= 0 frames");
+  const int E = M.cfg.input_dim;
+  RVCX_CHECK(E == C->hubert->cfg.embed_dim || (C->hubert->has_final_proj && E == C->hubert->final_proj.cout),
+             "the voice model's input_dim is neither the HuBERT's embed_dim (v2) nor its final_proj width (v1)");
+  if (C->index && C->index->dim != E)
+    fail("stream_open: the resident index holds " + std::to_string(C->index->dim) + "-wide vectors, the voice model takes " +
+         std::to_string(E) + "-wide features");
+  const long Nl = (long)Fc + Fx + Fs + Fb;
+  if (Nl > 6000) fail("stream_open: more than 60 s of context");
+  const int N = (int)Nl;
+  const int Th = hubert_frames(*C->hubert, (int64_t)N * 160);
+  if (Th <= 0) fail("stream_open: the ring is too short for the HuBERT");
+  const int T = std::min(N, 2 * Th);                 // p_len clamp, pipeline.py:257-262
+  const int Fk = Fb + Fx + Fs;
+  if (Fk > T)
+    fail("stream_open: block + cross-fade + search = " + std::to_string(Fk) + " frames exceed the " + std::to_string(T) +
+         " frames a step synthesizes from");
+  for (int s = 0; s < S; ++s)
+    if (sid[s] < 0 || sid[s] >= M.cfg.spk_embed_dim) fail("stream_open: speaker id out of range");
+  auto se = std::make_unique<StreamSession>();
+  se->model_id = model_id;
+  se->region = M.region;
+  se->cfg = *cfg;
+  se->p = *p;
+  se->sid.assign(sid, sid + S);
+  se->pitch.assign(pitch, pitch + S);
+  se->full_synth = getenv("RVCX_STREAM_FULL_SYNTH") && atoi(getenv("RVCX_STREAM_FULL_SYNTH")) != 0;
+  se->S = S, se->N = N, se->Th = Th, se->T = T, se->head = T - Fk, se->upp = M.upp, se->inter = M.cfg.inter_channels, se->E = E;
+  se->Lb = (long)Fb * M.upp, se->Lx = (long)Fx * M.upp, se->Ls = (long)Fs * M.upp, se->Lk = (long)Fk * M.upp;
+  RVCX_CHECK((size_t)se->inter * T < ((size_t)1 << 24) && (size_t)T * M.upp < ((size_t)1 << 24), "stream_open: step too long for its noise counters");
+  {
+    const size_t budget = stream_budget(*C);
+    if (stream_step_bytes(*C, M, *p, S, N, Th, T, se->Lk, se->Lb, se->Ls) > budget) {
+      int fit = S - 1;
+      while (fit > 0 && stream_step_bytes(*C, M, *p, fit, N, Th, T, se->Lk, se->Lb, se->Ls) > budget) --fit;
+      fail("stream_open: one step of " + std::to_string(S) + " streams does not fit the activation budget; the largest "
+           "n_streams that fits is " + std::to_string(fit));
+    }
+  }
+  const size_t ring_b = (size_t)S * N * 160 * 4, carry_b = (size_t)S * se->Lx * 4;
+  for (int k = 0; k < 2; ++k) {
+    RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&se->ring[k]), ring_b));
+    RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&se->carry[k]), carry_b));
+    RVCX_HIP(hipMemsetAsync(se->ring[k], 0, ring_b, C->stream));
+    RVCX_HIP(hipMemsetAsync(se->carry[k], 0, carry_b, C->stream));
+  }
+  RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&se->blocks), (size_t)S * Fb * 160 * 4));
+  RVCX_HIP(hipStreamSynchronize(C->stream));
+  const int id = ctx->next_session++;
+  ctx->sessions[id] = std::move(se);
+  *stream_id = id;
+  API_END
+}
+
+int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k, const float* const* noise,
+                     float* const* out, float* const* pre_sola, int32_t* offsets) {
+  CtxLock ctx_guard_ = lock_ctx(ctx);
+  StreamSession* done = nullptr;
+  const int rc = api_call(ctx, true, [&](Ctx* C) {
+    StreamSession& se = get_session(ctx, stream_id);
+    if (!block16k || !out) fail("stream_step: null argument");
+    if (se.region.expired() || se.model_id >= (int)C->synths.size() || !C->synths[se.model_id] ||
+        C->synths[se.model_id]->region != se.region.lock())
+      fail("stream_step: the session's voice model was unloaded; close the session");
+    if (!C->hubert) fail("stream_step: hubert not loaded");
+    check_f0_backend(*C, se.p);
+    SynthModel& M = *C->synths[se.model_id];
+    const int S = se.S, N = se.N, Th = se.Th, T = se.T, E = se.E, inter = se.inter;
+    const long n = (long)N * 160, blk = (long)se.cfg.block_frames * 160, Lb = se.Lb, Lx = se.Lx, Ls = se.Ls, Lk = se.Lk;
+    const bool use_index = C->index && se.p.index_rate != 0.f, use_protect = se.p.protect < 0.5f;
+    if (use_index && C->index->dim != E) fail("stream_step: the resident index does not match the voice model's input_dim");
+    for (int s = 0; s < S; ++s)
+      if (!block16k[s] || !out[s] || (noise && !noise[s]) || (pre_sola && !pre_sola[s])) fail("stream_step: null pointer in a table");
+    C->ensure_splitk(S);
+    C->arena.reserve(stream_step_bytes(*C, M, se.p, S, N, Th, T, Lk, Lb, Ls));
+    C->arena.reset();
+    hipStream_t st = C->stream;
+    Arena& A = C->arena;
+    if (se.full_synth && noise) fail("stream_step: RVCX_STREAM_FULL_SYNTH=1 sessions take no parity noise");
+    const long Lsyn = se.full_synth ? (long)T * M.upp : Lk;      // samples the synthesizer writes per stream
+    C->timer.make();
+    hipEvent_t* ev = C->timer.ev;        // {start, F0, HuBERT, blend + mix + noise = synthesizer start, enc_p, flow, decoder, SOLA + copies}
+    RVCX_HIP(hipEventRecord(ev[0], st));
+    // (1) the rings move left by one block
+    for (int s = 0; s < S; ++s)
+      RVCX_HIP(hipMemcpyAsync(se.blocks + (size_t)s * blk, block16k[s], (size_t)blk * 4, hipMemcpyDefault, st));
+    const float* ring_old = se.ring[se.cur];
+    float* ring = se.ring[se.cur ^ 1];
+    launch_ring_shift(ring_old, ring, se.blocks, S, n, blk, st);
+    // (2) VC.get_f0 on the whole ring, B = S; pitch shift and coarse quantisation with each stream's own pitch
+    int* dp = A.alloc<int>((size_t)S * T);
+    float* dpf = A.alloc<float>((size_t)S * T);
+    {
+      const size_t mk = A.mark();
+      const long F = 1 + n / 160;
+      float* fraw = A.alloc<float>((size_t)S * F);
+      if (se.p.f0_method == RVCX_F0_FCPE) {          // compute_f0(x, p_len = N), then the first T frames (pipeline.py:169-181)
+        int* cN = A.alloc<int>((size_t)S * N);
+        float* fN = A.alloc<float>((size_t)S * N);
+        fcpe_forward(*C, *C->fcpe, S, ring, n, 0.03f, fraw, nullptr, nullptr, st);
+        for (int s = 0; s < S; ++s)
+          fcpe_post_coarse(*C, fraw + (size_t)s * F, 1, (int)F, N, fN + (size_t)s * N, cN + (size_t)s * N, N, se.pitch[s],
+                           se.p.f0_min, se.p.f0_max, st);
+        launch_copy_strided(fN, dpf, S, T, N, T, st);
+        launch_copy_strided(reinterpret_cast<const float*>(cN), reinterpret_cast<float*>(dp), S, T, N, T, st);
+      } else {
+        rmvpe_forward(*C, *C->rmvpe, S, ring, n, 0.03f, se.p.f0_min, se.p.f0_max, fraw, nullptr, st);
+        for (int s = 0; s < S; ++s)
+          launch_f0_coarse(fraw + (size_t)s * F, dpf + (size_t)s * T, dp + (size_t)s * T, T, se.pitch[s], se.p.f0_min,
+                           se.p.f0_max, st);
+      }
+      A.reset(mk);       // (stream order: everything later on `st` runs behind these launches)
+    }
+    RVCX_HIP(hipEventRecord(ev[1], st));
+    // (3) VC.vc's front: HuBERT, retrieval blend, x2 upsample + protect mix
+    float* phone = A.alloc<float>((size_t)S * E * T);
+    float* zn = A.alloc<float>((size_t)S * inter * T);
+    float* sn = A.alloc<float>((size_t)S * Lsyn);
+    float* y = A.alloc<float>((size_t)S * Lsyn);
+    {
+      const size_t mk0 = A.mark();
+      float* feats = A.alloc<float>((size_t)S * E * Th);
+      {
+        const size_t mk = A.mark();
+        hubert_features_for(*C, *C->hubert, E, S, ring, n, feats, st);
+        A.reset(mk);
+      }
+      RVCX_HIP(hipEventRecord(ev[2], st));
+      const float* feats0 = feats;
+      if (use_index) {
+        if (use_protect) {
+          float* keep = A.alloc<float>((size_t)S * E * Th);
+          RVCX_HIP(hipMemcpyAsync(keep, feats, (size_t)S * E * Th * 4, hipMemcpyDeviceToDevice, st));
+          feats0 = keep;
+        }
+        for (int s = 0; s < S; ++s) {
+          const size_t mk = A.mark();
+          index_blend(*C, *C->index, feats + (size_t)s * E * Th, Th, se.p.index_rate, nullptr, nullptr, st);
+          A.reset(mk);
+        }
+      }
+      for (int s = 0; s < S; ++s)
+        launch_upsample_protect(feats + (size_t)s * E * Th, feats0 + (size_t)s * E * Th, dpf + (size_t)s * T,
+                                phone + (size_t)s * E * T, E, Th, T, se.p.protect, use_protect ? 1 : 0, st);
+      A.reset(mk0);
+    }
+    // the two Gaussian draws: parity noise, or Philox(seed + s) at counters no two steps share (2^23 quads per draw)
+    for (int s = 0; s < S; ++s) {
+      if (noise) {
+        RVCX_HIP(hipMemcpyAsync(zn + (size_t)s * inter * T, noise[s], (size_t)inter * T * 4, hipMemcpyDefault, st));
+        RVCX_HIP(hipMemcpyAsync(sn + (size_t)s * Lk, noise[s] + (size_t)inter * T, (size_t)Lk * 4, hipMemcpyDefault, st));
+      } else {
+        launch_randn(zn + (size_t)s * inter * T, (size_t)inter * T, se.p.seed + (uint64_t)s, se.step << 24, st);
+        launch_randn(sn + (size_t)s * Lsyn, (size_t)Lsyn, se.p.seed + (uint64_t)s, (se.step << 24) + ((uint64_t)1 << 23), st);
+      }
+    }
+    // (4) the synthesizer on the tail
+    SynthIO io;
+    io.B = S;
+    io.T = T;
+    io.phone_ct = phone;
+    io.pitch = dp;
+    io.pitchf = dpf;
+    io.sid_host = se.sid.data();
+    io.z_noise = zn;
+    io.src_noise = sn;
+    io.out = y;
+    io.skip_head = se.full_synth ? 0 : se.head;
+    synth_forward(*C, M, io, ev + 3);
+    // (5) SOLA per stream; the offset stays on the device
+    float* dout = A.alloc<float>((size_t)S * Lb);
+    float* dsc = A.alloc<float>((size_t)S * (Ls + 1));
+    int* doff = A.alloc<int>((size_t)S);
+    const float* tail = y + (Lsyn - Lk);                           // the last Fb + Fx + Fs frames of every row
+    launch_sola(tail, Lsyn, se.carry[se.cur], dout, Lb, se.carry[se.cur ^ 1], doff, dsc, S, (int)Lb, (int)Lx, (int)Ls, st);
+    for (int s = 0; s < S; ++s) {
+      RVCX_HIP(hipMemcpyAsync(out[s], dout + (size_t)s * Lb, (size_t)Lb * 4, hipMemcpyDefault, st));
+      if (pre_sola) RVCX_HIP(hipMemcpyAsync(pre_sola[s], tail + (size_t)s * Lsyn, (size_t)Lk * 4, hipMemcpyDefault, st));
+    }
+    if (offsets) RVCX_HIP(hipMemcpyAsync(offsets, doff, (size_t)S * 4, hipMemcpyDefault, st));
+    RVCX_HIP(hipEventRecord(ev[7], st));
+    C->snapshot_dev_err(st);
+    RVCX_HIP(hipStreamSynchronize(st));
+    C->check_dev_err();
+    {   // rvcx_last_timing: {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} of this step
+      float* ms = C->timing;
+      ms[0] = 0.f;
+      for (int k = 1; k <= 7; ++k) RVCX_HIP(hipEventElapsedTime(&ms[k], ev[k - 1], ev[k]));
+      RVCX_HIP(hipEventElapsedTime(&ms[8], ev[0], ev[7]));
+    }
+    A.reset();
+    done = &se;
+  });
+  if (rc == 0 && done) {      // the step stands: the sets written become the session's state
+    done->cur ^= 1;
+    done->step++;
+  }
+  return rc;
+}
+
+int rvcx_stream_reset(rvcx_ctx* ctx, int stream_id) {
+  API_BEGIN_ONCE(ctx)
+  StreamSession& se = get_session(ctx, stream_id);
+  RVCX_HIP(hipMemsetAsync(se.ring[se.cur], 0, (size_t)se.S * se.N * 160 * 4, C->stream));
+  RVCX_HIP(hipMemsetAsync(se.carry[se.cur], 0, (size_t)se.S * se.Lx * 4, C->stream));
+  RVCX_HIP(hipStreamSynchronize(C->stream));
+  se.step = 0;
+  API_END
+}
+
+int rvcx_stream_close(rvcx_ctx* ctx, int stream_id) {
+  API_BEGIN_ONCE(ctx)
+  (void)get_session(ctx, stream_id);
+  RVCX_HIP(hipDeviceSynchronize());
+  ctx->sessions.erase(stream_id);
+  API_END
+}
+
+static int64_t stream_query(rvcx_ctx* ctx, int stream_id, int what) {
+  CtxLock ctx_guard_ = lock_ctx(ctx);
+  if (!ctx) return -1;
+  auto it = ctx->sessions.find(stream_id);
+  if (it == ctx->sessions.end()) return -1;
+  const StreamSession& se = *it->second;
+  return what == 0 ? (int64_t)se.Lb : what == 1 ? (int64_t)se.inter * se.T + se.Lk : (int64_t)se.T;
+}
+int64_t rvcx_stream_out_len(rvcx_ctx* ctx, int stream_id) { return stream_query(ctx, stream_id, 0); }
+int64_t rvcx_stream_noise_len(rvcx_ctx* ctx, int stream_id) { return stream_query(ctx, stream_id, 1); }
+int rvcx_stream_frames(rvcx_ctx* ctx, int stream_id) { return (int)stream_query(ctx, stream_id, 2); }
 
 // The per-launch profile is PROCESS-wide state (conv.hip): the two hooks below serialise against each other on one mutex, but
 // launches of ANOTHER context that run while a profile is open are recorded into it too (rvcx.h says so).

@@ -388,7 +388,9 @@ __global__ __launch_bounds__(256) void blend_kernel(const float* fd_g, const int
 
 void index_blend(Ctx& c, const IndexData& ix, float* feats_ct, int T, float index_rate, int64_t* ids, float* dist,
                  hipStream_t s) {
-  RVCX_CHECK(ix.n >= TOPK, "index: fewer than 8 stored vectors");
+  // fewer than 8 stored vectors: index.search pads with id -1 / distance inf like a short inverted list does, and the
+  // reference reads big_npy[-1] with weight (1/inf)^2 = 0 (blend_kernel) -- every kernel below bounds its rows by ix.n
+  RVCX_CHECK(ix.n >= 1, "index: no stored vectors");
   RVCX_CHECK(ix.dim <= kMaxDim, "index: feature dimension above 1024");
   Arena& A = c.arena;
   float* dots = A.alloc<float>((size_t)ix.n * T);

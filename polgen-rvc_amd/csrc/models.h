@@ -67,6 +67,11 @@ struct SynthIO {
   // decoder call away at both ends (pipeline.py:432-447): with dec_skip <= t_pad frames - SynthModel::dec_rf_frames the
   // samples it keeps are the ones the full evaluation gives (the decoder is convolutional; its source is computed whole).
   int dec_skip = 0;
+  // Synthesizer.infer's `rate` (synthesizers.py:175-181) in frames: the TextEncoder and the z_p draw span all T frames, then z_p,
+  // the mask and pitchf are sliced to [skip_head:] and the flow, the harmonic source (its phase accumulation starts at the
+  // slice) and the decoder run at T - skip_head frames.  src_noise, out and z_out are then (B, (T - skip_head) * upp) /
+  // (B, inter, T - skip_head).  Equal lengths only, not together with dec_skip; 0 = the plain call.
+  int skip_head = 0;
   // optional taps for parity tests (device, may be null)
   float* stats_out = nullptr;         // (B, 2*inter, T) = [m_p ; logs_p]
   float* z_out = nullptr;             // (B, inter, T)

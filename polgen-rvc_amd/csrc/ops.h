@@ -143,6 +143,16 @@ void launch_resample_f64(const ResampleFilter& f, const double* x, long n, int c
                          hipStream_t s);
 void launch_resample_f32(const ResampleFilter& f, const float* x, long n, float* y, long n_out, hipStream_t s);
 
+// ---- stream.hip: live-stream sessions
+// rows (S, n) of 16 kHz samples: dst row = src row shifted left by `blk` samples with block s appended (src != dst).
+// blocks: device (S, blk)
+void launch_ring_shift(const float* src, float* dst, const float* blocks, int S, long n, long blk, hipStream_t s);
+// SOLA per stream (rvcx.h, rvcx_op_sola): y rows (Lb + Lx + Ls samples, y_bs apart), carry b_in (S, Lx) -> out rows (Lb
+// samples, out_bs apart), the new carry b_out (S, Lx; may alias b_in), offset (S, device) and scores (S, Ls + 1; scratch the
+// caller provides).  The summation order of a score depends on Lx alone.
+void launch_sola(const float* y, long y_bs, const float* b_in, float* out, long out_bs, float* b_out, int* offset,
+                 float* scores, int S, int Lb, int Lx, int Ls, hipStream_t s);
+
 // ---- pipeline glue
 // feats (C,T) -> x2 nearest upsample, protect mix; writes phone (C, 2T') cropped to p_len  [pipeline.py:252-270]
 // ld_in / ld_out (0 = Th / p_len): row strides of feats / out when the item sits in a wider batch row

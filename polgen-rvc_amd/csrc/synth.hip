@@ -224,6 +224,16 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
   Arena& A = c.arena;
   Timer3 tm(c, stage_ev);
   tm.mark(0);
+  // SynthIO::skip_head (synthesizers.py:175-181): the TextEncoder and the z_p draw span all T frames; z_p, the mask and the
+  // pitch are then sliced to [head:], and the flow, the harmonic source and the decoder run at Tk = T - head frames.  head = 0
+  // is the plain call: Tk == T, no slice, the same launches as ever.
+  const int head = io.skip_head, Tk = T - head;
+  RVCX_CHECK(head >= 0 && Tk > 0, "synth: skip_head outside [0, T)");
+  if (head > 0) {
+    RVCX_CHECK(io.dec_skip == 0, "synth: dec_skip and skip_head exclude each other");
+    if (io.lens_host)
+      for (int b = 0; b < B; ++b) RVCX_CHECK(io.lens_host[b] == T, "synth: skip_head needs equal lengths (every item T frames)");
+  }
 
   // per-stage valid lengths (ragged batches); null when every item spans the full T
   bool ragged = false;
@@ -247,7 +257,13 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
   // (latency-bound, 192-channel) TextEncoder and flow, and each stage's ConvTranspose1d adds its noise-conv
   // output as the epilogue residual -- the same (up + bias) + (noise + bias) sum the reference forms, without
   // a separate read-modify-write pass over the upsampled activations.
-  const long Tupp = (long)T * m.upp;
+  const long Tupp = (long)Tk * m.upp;
+  const float* pitchf = io.pitchf;
+  if (head > 0) {                      // nsff0[:, head:]: the phase accumulation of the source starts at the slice
+    float* pf = A.alloc<float>((size_t)B * Tk);
+    launch_copy_strided(io.pitchf + head, pf, B, Tk, T, Tk, s);
+    pitchf = pf;
+  }
   float* har = A.alloc<float>((size_t)B * Tupp);
   std::vector<float*> nz(m.stages.size(), nullptr);
   // Stages whose ConvTranspose1d runs on the streaming kernel (convt_thin.hip: k = 4, stride 2, C = 128 / 64 -- the two
@@ -274,9 +290,9 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
       RVCX_HIP(hipEventRecord(c.ev_src[0], s));
       RVCX_HIP(hipStreamWaitEvent(sn, c.ev_src[0], 0));
     }
-    double* sc = A.alloc<double>((size_t)B * T * 2);
-    launch_sine_source(io.pitchf, io.src_noise, har, B, T, m.upp, (float)cf.sr, m.lin_wb, lens, sc, sn);
-    long tt = T;
+    double* sc = A.alloc<double>((size_t)B * Tk * 2);
+    launch_sine_source(pitchf, io.src_noise, har, B, Tk, m.upp, (float)cf.sr, m.lin_wb, lens, sc, sn);
+    long tt = Tk;
     for (size_t i = 0; i < m.stages.size(); ++i) {
       const auto& S = m.stages[i];
       tt *= cf.up_rates[i];
@@ -357,6 +373,10 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
   float* z = A.alloc<float>((size_t)B * inter * T);
   float* z2 = A.alloc<float>((size_t)B * inter * T);
   launch_sample_z(stats, io.z_noise, z, B, inter, T, lens, s);
+  if (head > 0) {                      // z_p[:, :, head:] as a dense (B, inter, Tk) tensor
+    launch_copy_strided(z + head, z2, B * inter, Tk, T, Tk, s);
+    std::swap(z, z2);
+  }
   // speaker embedding g (B, gin)
   float* g = A.alloc<float>((size_t)B * gin);
   for (int b = 0; b < B; ++b)
@@ -373,33 +393,33 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
     float* gc = A.alloc<float>((size_t)B * 6 * hid);
     for (int f = 3; f >= 0; --f) {
       const auto& F = m.flows[f];
-      launch_flip_channels(z, z2, B, inter, T, s);
+      launch_flip_channels(z, z2, B, inter, Tk, s);
       std::swap(z, z2);
-      ConvArgs a = conv1d_args(F.pre, z, h, B, T, T);
-      a.x_bs = (long)inter * T;          // reads only the first `half` channels of z
+      ConvArgs a = conv1d_args(F.pre, z, h, B, Tk, Tk);
+      a.x_bs = (long)inter * Tk;          // reads only the first `half` channels of z
       a.lens_out = lens;
       c.conv(a);
       a = conv1d_args(F.cond, g, gc, B, 1, 1);
       c.conv(a);
       for (int i = 0; i < 3; ++i) {
-        a = conv1d_args(F.in_l[i], h, xin, B, T, T, 1, 1, (F.in_l[i].k - 1) / 2);
+        a = conv1d_args(F.in_l[i], h, xin, B, Tk, Tk, 1, 1, (F.in_l[i].k - 1) / 2);
         a.lens_in = lens;
         a.lens_out = lens;
         c.conv(a);
-        launch_wn_gate(xin, gc, i * 2 * hid, 6 * hid, acts, B, hid, T, s);
-        a = conv1d_args(F.rs_l[i], acts, rs, B, T, T);
+        launch_wn_gate(xin, gc, i * 2 * hid, 6 * hid, acts, B, hid, Tk, s);
+        a = conv1d_args(F.rs_l[i], acts, rs, B, Tk, Tk);
         a.lens_out = lens;
         c.conv(a);
-        launch_wn_res_skip(h, wout, rs, B, hid, T, i == 2, i == 0, lens, s);
+        launch_wn_res_skip(h, wout, rs, B, hid, Tk, i == 2, i == 0, lens, s);
       }
-      a = conv1d_args(F.post, wout, mbuf, B, T, T);
+      a = conv1d_args(F.post, wout, mbuf, B, Tk, Tk);
       a.lens_out = lens;
       c.conv(a);
-      launch_coupling_sub(z, mbuf, B, half, T, lens, s);
+      launch_coupling_sub(z, mbuf, B, half, Tk, lens, s);
     }
   }
   if (io.z_out)
-    RVCX_HIP(hipMemcpyAsync(io.z_out, z, (size_t)B * inter * T * sizeof(float), hipMemcpyDeviceToDevice, s));
+    RVCX_HIP(hipMemcpyAsync(io.z_out, z, (size_t)B * inter * Tk * sizeof(float), hipMemcpyDeviceToDevice, s));
   tm.mark(2);
   if (io.ev_decoder) RVCX_HIP(hipEventRecord(io.ev_decoder, s));
 
@@ -428,16 +448,16 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
     // One utterance at a time -- or a group of EQUAL length -- runs at ITS OWN length Td (rows of the batched tensors stay T
     // apart): no masks, no work on padding, and every launch decision (tile, split-K) is the one the utterance's single run takes.
     const bool own = io.lens_host != nullptr && (db == 1 || equal_lens);
-    const int Tfull = own ? io.lens_host[b0] : T;
-    RVCX_CHECK(Tfull > 0 && Tfull <= T, "synth: item length outside (0, T]");
+    const int Tfull = own ? io.lens_host[b0] - head : Tk;
+    RVCX_CHECK(Tfull > 0 && Tfull <= Tk, "synth: item length outside (0, T]");
     // the window of frames the decoder evaluates (SynthIO::dec_skip): [skip, Tfull - skip) of every member of the group
     const int skip = (io.dec_skip > 0 && (own || !lens) && Tfull - 2 * io.dec_skip > 2 * m.dec_rf_frames) ? io.dec_skip : 0;
     const int Td = Tfull - 2 * skip;
     float* cur = A.alloc<float>((size_t)db * C0 * Td);
     {
-      ConvArgs a = conv1d_args(m.conv_pre, z + (size_t)b0 * inter * T + skip, cur, db, Td, Td, 1, 1, 3);
-      a.x_bs = (long)inter * T;
-      a.x_cs = T;
+      ConvArgs a = conv1d_args(m.conv_pre, z + (size_t)b0 * inter * Tk + skip, cur, db, Td, Td, 1, 1, 3);
+      a.x_bs = (long)inter * Tk;
+      a.x_cs = Tk;
       a.lens_in = (lens && !own) ? lens + b0 : nullptr;
       c.conv(a);
       float* gcond = A.alloc<float>((size_t)db * C0);
@@ -445,7 +465,7 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
       c.conv(a);
       launch_add_channel_bias(cur, gcond, db, C0, Td, s);
     }
-    long Tin = Td, Tin_c = T, off = skip;      // off: first sample of the window at this stage's rate
+    long Tin = Td, Tin_c = Tk, off = skip;      // off: first sample of the window at this stage's rate
     for (size_t i = 0; i < m.stages.size(); ++i) {
       const auto& S = m.stages[i];
       const long Tout = Tin * cf.up_rates[i], Tout_c = Tin_c * cf.up_rates[i];
@@ -623,10 +643,10 @@ void synth_forward(Ctx& c, const SynthModel& m, const SynthIO& io, hipEvent_t* s
       a.lens_out = a.lens_in;
       a.y_bs = (long)Tupp;             // output rows are T * upp apart whatever the group's own length
       c.conv(a);
-      if (skip + Td < T)               // the rest of each item's output row reads as silence
+      if (skip + Td < Tk)              // the rest of each item's output row reads as silence
         for (int q = 0; q < db; ++q)
           RVCX_HIP(hipMemsetAsync(io.out + (size_t)(b0 + q) * Tupp + (size_t)(skip + Td) * m.upp, 0,
-                                  (size_t)(T - skip - Td) * m.upp * sizeof(float), s));
+                                  (size_t)(Tk - skip - Td) * m.upp * sizeof(float), s));
       if (skip)                        // and so does what lies in front of the window
         for (int q = 0; q < db; ++q)
           RVCX_HIP(hipMemsetAsync(io.out + (size_t)(b0 + q) * Tupp, 0, (size_t)skip * m.upp * sizeof(float), s));

@@ -357,6 +357,44 @@ class VC:
             return (res[0][0], res[1][0]) if return_f32 else res[0]
         return res
 
+    @staticmethod
+    def _stream_frames(block_ms, context_ms, crossfade_ms, search_ms):
+        """the geometry of a live-stream session in 10 ms frames (the step of the F0 models and of the synthesizer)"""
+        out = []
+        for name, ms, low in (("block_ms", block_ms, 1), ("context_ms", context_ms, 0), ("crossfade_ms", crossfade_ms, 1),
+                              ("search_ms", search_ms, 0)):
+            f = float(ms) / 10.0
+            if f != int(f) or int(f) < low:
+                raise ValueError(f"{name}={ms!r}: a multiple of 10 ms, at least {10 * low} ms")
+            out.append(int(f))
+        return tuple(out)
+
+    def stream_open(self, model, net_g, sids, pitches, f0_method, file_index, index_rate, version, protect, *,
+                    block_ms, context_ms, crossfade_ms, search_ms, f0_min=50, f0_max=1100):
+        """A live-stream session: len(sids) lock-step streams of one geometry on voice model ``net_g``.  Every
+        ``session.step(blocks)`` takes one (S, block_ms * 16) float32 block of 16 kHz mono audio per stream and returns the
+        converted (S, block_ms * tgt_sr / 1000) float32 blocks: rolling context, tail-only synthesis (Synthesizer.infer's
+        ``rate``) and SOLA on the device.  No high-pass, volume envelope, resample_sr or peak normalisation: those are
+        whole-clip operations of ``pipeline``.  Checks of version, method and index as in ``pipeline_batch``."""
+        self._check_method(f0_method)
+        if f0_method == "mangio-crepe":
+            raise ValueError("mangio-crepe is not available to live streams (Viterbi pass and host dither per clip); "
+                             "use rmvpe, rmvpe+ or fcpe")
+        self._check_version(version, net_g)
+        Fb, Fc, Fx, Fs = self._stream_frames(block_ms, context_ms, crossfade_ms, search_ms)
+        sids = [int(v) for v in np.atleast_1d(_np(sids)).ravel()]
+        pitches = [float(v) for v in np.atleast_1d(_np(pitches)).ravel()]
+        if not sids or len(sids) != len(pitches):
+            raise ValueError("stream_open: one speaker id and one pitch (semitones) per stream")
+        ctx = net_g.ctx
+        if model.ctx is not ctx:
+            raise ValueError("hubert and voice model live on different rvcx contexts")
+        self._ensure_f0_model(f0_method, ctx)
+        index, _ = self._load_index(ctx, file_index, index_rate)
+        p = self._params(0.0, index_rate if index is not None else 0.0, 1.0, protect, f0_min, f0_max, sids[0],
+                         f0_method=f0_method)
+        return ctx.stream_open(net_g.model_id, p, sids, pitches, Fb, Fc, Fx, Fs)
+
     def pipeline_async(self, model, net_g, sid, audio, input_audio_path, pitch, f0_method, file_index, index_rate,
                        pitch_guidance, filter_radius, tgt_sr, resample_sr, volume_envelope, version, protect,
                        hop_length, f0_file, f0_min=50, f0_max=1100, *, noise=None, return_f32=False, crepe_dither=None):

@@ -210,6 +210,50 @@ def gold_synth(tag, cfg, T, seed, outliers=False):
                         z_p=z_p.numpy(), z=z.numpy(), audio=o.numpy())
 
 
+def gold_synth_head(tag, cfg, T, seed, rate):
+    """Synthesizer.infer(..., rate=torch.tensor(rate)) (synthesizers.py:175-181): the flow, the source and the decoder see
+    frames [head:] only.  Inputs as gold_synth draws them; the first randn_like draw is (1, inter, T), the second
+    (1, (T - head) * upp, 1).  audio_full_tail: the tail of the FULL evaluation with the same z_noise (and a source noise
+    whose tail is src_noise) -- what slicing a plain call would give, the negative control of the GPU test."""
+    from polgen_rvc_amd._lib import head_from_rate
+    sd = S.to_torch(S.synth_state(cfg, seed))
+    net = ref_synth(cfg, sd)
+    c = O_synth.cfg_fields(cfg)
+    g = torch.Generator().manual_seed(100 + seed)
+    phone = torch.randn(1, T, 768, generator=g)
+    pitch = torch.randint(1, 256, (1, T), generator=g)
+    f0 = 100 + 300 * torch.rand(1, T, generator=g)
+    f0[:, T // 3: T // 3 + max(2, T // 8)] = 0          # an unvoiced stretch
+    pitch[f0 == 0] = 1
+    z_noise = torch.randn(1, c["inter"], T, generator=g)
+    src_full = torch.randn(1, T * c["upp"], 1, generator=g)
+    r = torch.tensor(rate)                               # float32, as a caller of the reference passes it
+    head = int(T * (1.0 - r.item()))
+    assert head == head_from_rate(T, rate), (head, head_from_rate(T, rate))
+    print(f"[synth_head {tag}] T={T} rate={rate} head={head}")
+    src_noise = src_full[:, head * c["upp"]:].contiguous()
+    orig = torch.randn_like
+
+    def run(draws, **kw):
+        it = iter(draws)
+        torch.randn_like = lambda x, **k2: next(it)
+        try:
+            return net.infer(phone, torch.tensor([T]), pitch, f0, torch.tensor([0]), **kw)
+        finally:
+            torch.randn_like = orig
+    o, x_mask, (z, z_p, m_p, logs_p) = run([z_noise, src_noise], rate=r)
+    assert o.shape[-1] == (T - head) * c["upp"] and z.shape[-1] == T - head, (o.shape, z.shape)
+    o_full = run([z_noise, src_full])[0]
+    tail = o_full[..., head * c["upp"]:]
+    # oracle/synth.py restates rate=None only: the sliced result is the reference's alone
+    print(f"  reference only (the oracle has no slice): rms(audio)={rms(o):.4e}, tail of the full evaluation differs by "
+          f"{rms(o - tail):.3e} rms = {rms(o - tail) / rms(o):.3f} relative")
+    np.savez_compressed(os.path.join(GOLD, f"synth_head_{tag}.npz"), seed=seed, cfg=json.dumps(cfg), rate=np.float32(rate),
+                        head=head, phone=phone.numpy(), pitch=pitch.numpy(), f0=f0.numpy(), z_noise=z_noise.numpy(),
+                        src_noise=src_noise.numpy().astype(np.float32), z=z.numpy(), audio=o.numpy(),
+                        audio_full_tail=tail.numpy())
+
+
 def stable_seed(rcfg, audio_pad_f32, seed, f0_min=50, f0_max=1100, pitch=0.0, tries=40):
     """First seed >= `seed` (step 100) for which every frame's f0 decision is well-conditioned (None if `tries`
     seeds were not enough)."""
@@ -756,6 +800,10 @@ def main():
         "layouts": gold_layouts,
         "synth_tiny": lambda: gold_synth("tiny", S.SYNTH_CFG_TINY, 37, 1),
         "synth_48k": lambda: gold_synth("48k_T24", S.SYNTH_CFG_48K, 24, 0),
+        # Synthesizer.infer's `rate` (live streams): head = int(T * (1 - float32(rate))) -- 40 * (1 - 0.3f) is 27, not 28
+        "synth_head_h30": lambda: gold_synth_head("tiny_h30", S.SYNTH_CFG_TINY, 40, 3, 0.25),
+        "synth_head_h27": lambda: gold_synth_head("tiny_h27", S.SYNTH_CFG_TINY, 40, 3, 0.3),
+        "synth_head_48k": lambda: gold_synth_head("48k_h15", S.SYNTH_CFG_48K, 24, 0, 0.375),
         "rmvpe_tiny": lambda: gold_rmvpe("tiny", S.RMVPE_CFG_TINY, 0.7, 1),
         "rmvpe_full": lambda: gold_rmvpe("full_1s", S.RMVPE_CFG_FULL, 1.0, 0),
         "rmvpe_illcond": gold_rmvpe_illcond,

@@ -4,7 +4,7 @@ RVCX_LIBRARY=build/asan/librvcx_asan.so).  The library's HIP runtime is tools/hi
 kernels do not run, so outputs are meaningless -- what is exercised under AddressSanitizer + UBSan is the host code:
 checkpoint folding / packing for all five model kinds (+ both index kinds), weight regions (free / reload / clone /
 adopt), the micro-batch planner over BASELINE configs[4]'s 256 lengths, bucket lengths, the chunk planner of clips longer
-than x_max, the f0-file track, arena arithmetic, error paths, the FLAC codec.  Prints HOST_ASAN_OK at the end."""
+than x_max, the f0-file track, arena arithmetic, error paths, the lifecycle of live-stream sessions, the FLAC codec.  Prints HOST_ASAN_OK at the end."""
 import os
 import sys
 
@@ -41,6 +41,70 @@ def load_all(ctx, full):
     for scfg in ([S.SYNTH_CFG_48K, S.SYNTH_CFG_40K] if full else [S.SYNTH_CFG_TINY]):
         mids.append(ctx.load_synth(W.synth_cfg_struct(scfg, hcfg["embed_dim"]), S.synth_state(scfg, 4, input_dim=hcfg["embed_dim"])))
     return hcfg, mids
+
+
+# ---- live-stream sessions: open, three steps, reset, close; a step after unload_synth; a step with a ticket in flight;
+# every refusal of open; destroy with a session open (further down)
+def stream_lifecycle(ctx, mid, hcfg, clips, params):
+    Fb, Fc, Fx, Fs = 6, 20, 2, 1
+    blk = np.stack([clips[1][:Fb * 160], clips[2][:Fb * 160]]).astype(np.float32)
+    with ctx.stream_open(mid, params(seed=3), [0, 1], [0.0, 2.0], Fb, Fc, Fx, Fs) as se:
+        assert se.frames == 28 and se.skip_head == 19 and se.n_streams == 2
+        for k in range(3):
+            out = se.step(blk)
+            assert out.shape == (2, se.block_out)
+        out, pre, offs = se.step(blk, noise=np.zeros((2, se.noise_len), np.float32), taps=True)
+        assert pre.shape == (2, se.tail_len) and offs.shape == (2,)
+        se.reset()
+        se.step(blk)
+        t = ctx.convert_submit(mid, [clips[0]], params())        # a step completes the ticket in flight first
+        se.step(blk)
+        assert ctx.convert_inflight() == 0
+        t.wait()
+        for bad in (lambda: se.step(blk[:1]), lambda: se.step(blk, noise=np.zeros((2, 3), np.float32))):
+            try:
+                bad()
+                raise SystemExit("misuse was accepted")
+            except _lib.RvcxError:
+                pass
+    assert L.rvcx_stream_step(ctx._h, 12345, None, None, None, None, None) == -1
+    assert L.rvcx_stream_close(ctx._h, 12345) == -1 and L.rvcx_stream_reset(ctx._h, 12345) == -1
+    assert L.rvcx_stream_out_len(ctx._h, 12345) == -1 and L.rvcx_stream_frames(ctx._h, 12345) == -1
+    scfg = S.SYNTH_CFG_TINY
+    gone = ctx.load_synth(W.synth_cfg_struct(scfg, hcfg["embed_dim"]), S.synth_state(scfg, 6, input_dim=hcfg["embed_dim"]))
+    se = ctx.stream_open(gone, params(), [0], [0.0], Fb, Fc, Fx, Fs)
+    se.step(blk[:1])
+    ctx.unload_synth(gone)
+    try:
+        se.step(blk[:1])
+        raise SystemExit("a step on an unloaded voice model was accepted")
+    except _lib.RvcxError as e:
+        assert "unloaded" in str(e)
+    se.close()
+    for geo, kw in (((Fb, 0, Fx, Fs), {}), ((0, Fc, Fx, Fs), {}), ((Fb, Fc, 0, Fs), {}), ((Fb, Fc, Fx, Fs), dict(f0_method=_lib.F0_CREPE)),
+                    ((Fb, 7000, Fx, Fs), {})):
+        try:
+            ctx.stream_open(mid, params(**kw), [0], [0.0], *geo)
+            raise SystemExit("a bad session was opened")
+        except _lib.RvcxError:
+            pass
+    ctx.load_index(S.make_index(16, hcfg["embed_dim"] + 8, 1))
+    try:
+        ctx.stream_open(mid, params(), [0], [0.0], Fb, Fc, Fx, Fs)
+        raise SystemExit("an index of another width was accepted")
+    except _lib.RvcxError:
+        pass
+    ctx.load_index(S.make_index(6, hcfg["embed_dim"], 1))
+    with ctx.stream_open(mid, params(index_rate=0.5), [0], [0.0], Fb, Fc, Fx, Fs) as se:
+        se.step(blk[:1])
+    ctx.load_index(None)
+    y = np.zeros(11 + 37 + 5, np.float32)
+    out, carry, off, sc = ctx.sola(y, np.ones(37, np.float32), 11, 37, 5, scores=True)
+    assert out.shape == (11,) and carry.shape == (37,) and sc.shape == (6,)
+    ph = np.zeros((2, 28, hcfg["embed_dim"]), np.float32)
+    o, z = ctx.synth_infer(mid, ph, np.ones((2, 28), np.int32), np.zeros((2, 28), np.float32), skip_head=19,
+                           z_noise=np.zeros((2, S.SYNTH_CFG_TINY[2], 28), np.float32))
+    assert o.shape[1] == 9 * ctx.synth_upp(mid) and z.shape[2] == 9
 
 
 # ---- tiny models with real (random) values: folding, packing, fp16 images, legacy weight-norm names, fp16 tensors
@@ -85,6 +149,9 @@ with S.shapes_only():
 ctx2.weights_clone(ctx)
 ctx2.weights_adopt()
 ctx2.convert_batch(0, clips[:2], params())
+stream_lifecycle(ctx, mids[0], hcfg, clips, params)
+open_session = ctx2.stream_open(0, params(), [0, 0], [0.0, 1.0], 6, 20, 2, 1)      # destroy with a session open
+open_session.step(np.zeros((2, 960), np.float32))
 # error paths: nothing may be read or written out of bounds on the way to the error code
 for bad in (lambda: ctx.convert_batch(99, clips[:1], params()), lambda: ctx.convert_batch(mids[0], [np.zeros(0, np.float32)], params()),
             lambda: ctx2.weights_clone(ctx2) if False else ctx.load_synth(W.synth_cfg_struct(S.SYNTH_CFG_TINY, hcfg["embed_dim"]), {"x": np.zeros(3, np.float32)})):

@@ -3,7 +3,7 @@
 the sanitizer build, whose HIP runtime is tools/hipstub: kernels do not run, so sample values are meaningless).  What is
 exercised is the host code of rvcx_convert_submit / _wait / _poll / _inflight: four threads sharing one context for a few
 hundred tickets, the third-submit rule, loads and unloads between submits, every misuse path, destroy with tickets in
-flight, and out_n / last_cuts / last_micro_batches of each ticket against the synchronous call's.  Prints
+flight, live-stream sessions beside the tickets, and out_n / last_cuts / last_micro_batches of each ticket against the synchronous call's.  Prints
 HOST_TICKETS_OK at the end."""
 import os
 import sys
@@ -129,6 +129,72 @@ assert L.rvcx_convert_submit(ctx._h, mid, 1, None, 0, None, None, None, None, No
 t = ctx.convert_submit(mid, [], params())               # an empty ticket is a ticket
 assert t.wait() == []
 
+# ---- live-stream sessions: open, three steps, reset, close; a step after unload_synth; a step with a ticket in flight;
+# every refusal of open; destroy with a session open (further down)
+def stream_lifecycle(ctx, mid, hcfg, clips, params):
+    Fb, Fc, Fx, Fs = 6, 20, 2, 1
+    blk = np.stack([clips[1][:Fb * 160], clips[2][:Fb * 160]]).astype(np.float32)
+    with ctx.stream_open(mid, params(seed=3), [0, 1], [0.0, 2.0], Fb, Fc, Fx, Fs) as se:
+        assert se.frames == 28 and se.skip_head == 19 and se.n_streams == 2
+        for k in range(3):
+            out = se.step(blk)
+            assert out.shape == (2, se.block_out)
+        out, pre, offs = se.step(blk, noise=np.zeros((2, se.noise_len), np.float32), taps=True)
+        assert pre.shape == (2, se.tail_len) and offs.shape == (2,)
+        se.reset()
+        se.step(blk)
+        t = ctx.convert_submit(mid, [clips[0]], params())        # a step completes the ticket in flight first
+        se.step(blk)
+        assert ctx.convert_inflight() == 0
+        t.wait()
+        for bad in (lambda: se.step(blk[:1]), lambda: se.step(blk, noise=np.zeros((2, 3), np.float32))):
+            try:
+                bad()
+                raise SystemExit("misuse was accepted")
+            except _lib.RvcxError:
+                pass
+    assert L.rvcx_stream_step(ctx._h, 12345, None, None, None, None, None) == -1
+    assert L.rvcx_stream_close(ctx._h, 12345) == -1 and L.rvcx_stream_reset(ctx._h, 12345) == -1
+    assert L.rvcx_stream_out_len(ctx._h, 12345) == -1 and L.rvcx_stream_frames(ctx._h, 12345) == -1
+    scfg = S.SYNTH_CFG_TINY
+    gone = ctx.load_synth(W.synth_cfg_struct(scfg, hcfg["embed_dim"]), S.synth_state(scfg, 6, input_dim=hcfg["embed_dim"]))
+    se = ctx.stream_open(gone, params(), [0], [0.0], Fb, Fc, Fx, Fs)
+    se.step(blk[:1])
+    ctx.unload_synth(gone)
+    try:
+        se.step(blk[:1])
+        raise SystemExit("a step on an unloaded voice model was accepted")
+    except _lib.RvcxError as e:
+        assert "unloaded" in str(e)
+    se.close()
+    for geo, kw in (((Fb, 0, Fx, Fs), {}), ((0, Fc, Fx, Fs), {}), ((Fb, Fc, 0, Fs), {}), ((Fb, Fc, Fx, Fs), dict(f0_method=_lib.F0_CREPE)),
+                    ((Fb, 7000, Fx, Fs), {})):
+        try:
+            ctx.stream_open(mid, params(**kw), [0], [0.0], *geo)
+            raise SystemExit("a bad session was opened")
+        except _lib.RvcxError:
+            pass
+    ctx.load_index(S.make_index(16, hcfg["embed_dim"] + 8, 1))
+    try:
+        ctx.stream_open(mid, params(), [0], [0.0], Fb, Fc, Fx, Fs)
+        raise SystemExit("an index of another width was accepted")
+    except _lib.RvcxError:
+        pass
+    ctx.load_index(S.make_index(6, hcfg["embed_dim"], 1))
+    with ctx.stream_open(mid, params(index_rate=0.5), [0], [0.0], Fb, Fc, Fx, Fs) as se:
+        se.step(blk[:1])
+    ctx.load_index(None)
+    y = np.zeros(11 + 37 + 5, np.float32)
+    out, carry, off, sc = ctx.sola(y, np.ones(37, np.float32), 11, 37, 5, scores=True)
+    assert out.shape == (11,) and carry.shape == (37,) and sc.shape == (6,)
+    ph = np.zeros((2, 28, hcfg["embed_dim"]), np.float32)
+    o, z = ctx.synth_infer(mid, ph, np.ones((2, 28), np.int32), np.zeros((2, 28), np.float32), skip_head=19,
+                           z_noise=np.zeros((2, S.SYNTH_CFG_TINY[2], 28), np.float32))
+    assert o.shape[1] == 9 * ctx.synth_upp(mid) and z.shape[2] == 9
+
+
+stream_lifecycle(ctx, mid, S.HUBERT_CFG_TINY, clips, params)
+
 # ---- four threads share the context: submit / poll / wait, a few hundred tickets, some waited for by another thread
 errors, handoff, hand_lock = [], [], threading.Lock()
 
@@ -163,7 +229,23 @@ def worker(k):
         errors.append(repr(e))
 
 
+
+
+def stream_worker():
+    """a live session stepping while the four ticket threads submit and wait: every step finds the context to itself"""
+    try:
+        blk = np.stack([clips[1][:960], clips[2][:960]]).astype(np.float32)
+        with ctx.stream_open(mid, params(seed=5), [0, 1], [0.0, 1.0], 6, 20, 2, 1) as se:
+            for it in range(40):
+                assert se.step(blk).shape == (2, se.block_out)
+                if it == 20:
+                    se.reset()
+    except BaseException as e:  # noqa: BLE001
+        errors.append(repr(e))
+
+
 threads = [threading.Thread(target=worker, args=(k,)) for k in range(4)]
+threads.append(threading.Thread(target=stream_worker))
 for th in threads:
     th.start()
 for th in threads:
@@ -176,6 +258,8 @@ assert ctx.convert_inflight() == 0
 # ---- destroy with tickets in flight (and one dropped unwaited)
 c2 = _lib.Context(0)
 m2 = load(c2)
+open_session = c2.stream_open(m2, params(), [0], [0.0], 6, 20, 2, 1)      # and with a session open
+open_session.step(clips[1][None, :960].astype(np.float32))
 keep = [c2.convert_submit(m2, [clips[i]], params()) for i in (0, 3)]
 c2.close()
 for t in keep:
