@@ -406,7 +406,7 @@ class Context:
         if rc != 0:
             raise RvcxError("rvcx_create: " + (lib().rvcx_last_error(None) or b"").decode())
         self.device = device
-        # Every C entry point takes the context's own mutex (csrc/api.hip), so threads that share this object queue
+        # Every C entry point takes the context's own mutex (csrc/api_internal.h), so threads that share this object queue
         # instead of racing.  Multi-call sequences that must not interleave -- "make this index resident, then convert
         # with it" in the mirror's VC.pipeline -- hold this lock around the whole sequence.
         self.lock = threading.RLock()

@@ -1,0 +1,229 @@
+// What the api*.hip files share: the context handle, the per-call wrapper (api_call) and a few small helpers.
+#pragma once
+#include "../../include/rvcx.h"
+
+#include <atomic>
+#include <cmath>
+#include <cstdlib>
+#include <deque>
+#include <mutex>
+#include <unordered_map>
+
+#include "ctx.h"
+#include "layers.h"
+#include "models.h"
+#include "ops.h"
+#include "pipeline.h"
+
+// everything here but the handle itself (the C ABI names `struct rvcx_ctx`) lives in rvcx::api
+namespace rvcx {
+namespace api {
+
+// One context = one set of streams, arenas and resident models.  The reference builds fresh model objects for every
+// request (rvc/scripts/voice_conversion.py:71-100), so two Gradio worker threads never share state there; here every
+// thread of a process shares the one resident context (infer/_state.py) and ctypes releases the GIL -- so every entry
+// point takes the context's mutex (recursive: an entry point may call another).  Calls on one context QUEUE; throughput
+// comes from rvcx_convert_batch (one call, many utterances), not from threads.  Different contexts stay concurrent.
+// A conversion ticket (rvcx_convert_submit): the enqueue half of a conversion has run, the finish half runs when somebody
+// waits for it (or when something else needs the context to itself).  It owns copies of the small host-side arguments; the
+// audio, noise, dither and output buffers stay the caller's.
+struct Ticket {
+  rvcx_ticket id = 0;
+  enum State { InFlight, Done, Failed } state = InFlight;
+  std::string error;
+  int model_id = 0;
+  rvcx_params p;
+  std::vector<UttIO> ios;
+  std::vector<std::vector<float>> f0_rows;    // the f0-file tables `extra` pointed to
+  std::vector<int64_t> n_out;                 // produced samples per utterance (what out_n receives)
+  int64_t* out_n = nullptr;
+  bool inject_gru = false;                    // rvcx_debug_inject(1) was pending when the ticket was submitted: it is this ticket's
+  bool timing = false;
+  float ms[9] = {0};
+  TicketIO io;
+  ConvertStatePtr st;
+  bool enqueued = false;                      // ev_first / ev_done were recorded
+  std::shared_ptr<Ticket> prev;               // the ticket in flight in front of this one at submit time (lead_ms)
+  float lead_ms = 0.f;
+  std::vector<int> mbs;
+  std::vector<std::vector<long>> cuts;
+  ~Ticket() {
+    st.reset();
+    if (io.ev_first) (void)hipEventDestroy(io.ev_first);
+    if (io.ev_done) (void)hipEventDestroy(io.ev_done);
+  }
+};
+using TicketPtr = std::shared_ptr<Ticket>;
+
+// A live-stream session (rvcx_stream_open): S lock-step streams of one geometry on one voice model.  Ring, carry and block
+// staging are allocations of the session's own (the arena is scratch that other calls reset).  Ring and carry exist twice: a
+// step reads set `cur` and writes the other one, and the sets change places once the step has succeeded -- the body of a step
+// can then be repeated (range guard, BiGRU fallback) or fail without moving the session.
+struct StreamSession {
+  int model_id = 0;
+  std::weak_ptr<WeightRegion> region;      // expires when the voice model is unloaded (or replaced)
+  rvcx_stream_cfg cfg{};
+  rvcx_params p{};
+  std::vector<int> sid;
+  std::vector<float> pitch;
+  int S = 0, N = 0, Th = 0, T = 0, head = 0, upp = 0, inter = 0, E = 0;
+  long Lb = 0, Lx = 0, Ls = 0, Lk = 0;     // block, cross-fade, search and synthesized tail in output samples
+  float* ring[2] = {nullptr, nullptr};     // (S, N * 160) each
+  float* carry[2] = {nullptr, nullptr};    // (S, Lx) each
+  float* blocks = nullptr;                 // (S, Fb * 160): the step's new blocks, dense
+  int cur = 0;
+  uint64_t step = 0;
+  // RVCX_STREAM_FULL_SYNTH=1 (read at open; tools/bench_stream.py's A/B): the synthesizer runs with skip_head = 0 and SOLA takes
+  // the tail of the whole output -- what the step costs without the tail-only path (and NOT what the reference computes)
+  bool full_synth = false;
+  ~StreamSession() {
+    for (float* q : {ring[0], ring[1], carry[0], carry[1], blocks})
+      if (q) (void)hipFree(q);
+  }
+};
+
+}  // namespace api
+}  // namespace rvcx
+
+struct rvcx_ctx {
+  rvcx::Ctx c;
+  std::unordered_map<int, std::unique_ptr<rvcx::api::StreamSession>> sessions;
+  int next_session = 1;
+  std::recursive_mutex mu;
+  std::deque<rvcx::api::TicketPtr> inflight;                          // submit order; at most two
+  std::unordered_map<rvcx_ticket, rvcx::api::TicketPtr> tickets;      // every ticket that has not been waited for
+  std::deque<std::pair<rvcx_ticket, float>> leads;         // lead_ms of the tickets waited for last
+  rvcx::Arena load_arena;     // rvcx_resample_f64* with tickets in flight: a buffer nobody else uses (see there)
+};
+namespace rvcx {
+namespace api {
+
+using CtxLock = std::unique_lock<std::recursive_mutex>;
+inline CtxLock lock_ctx(rvcx_ctx* h) { return h ? CtxLock(h->mu) : CtxLock(); }
+
+inline thread_local std::string g_last_error;
+
+// Every entry point's body runs inside api_call():
+//  * fp16-split range guard.  If a split-fp16 kernel reported an activation it could not represent
+//    (Ctx::take_overflow), the FIRST offending layer of the call (launch order; every layer stamps its own device
+//    word) is pinned to the exact-fp32 kernels for the life of its model and the call is repeated -- a one-off per
+//    model and layer (rvcx_fp32_reruns counts the repeats, rvcx_fp32_layers the pinned layers).  If no layer can be
+//    named (kernel-level test entry points pack their weights per call) or after kMaxAttempts - 1 repeats, the last
+//    attempt runs everything on the exact-fp32 kernels (thread-local g_force_fp32).
+//  * BiGRU cluster time-out.  The cluster kernel needs its workgroups co-resident; if a partner never showed up
+//    (Ctx::check_dev_err -> GruTimeout) the call is repeated once with the single-workgroup GRU kernel.
+// Bodies are written to be repeatable (they reset the arena first); load / unload entry points run once (repeat = false).
+struct Fp32Scope {
+  bool saved;
+  explicit Fp32Scope(bool on) : saved(g_force_fp32) { g_force_fp32 = saved || on; }
+  ~Fp32Scope() { g_force_fp32 = saved; }
+};
+struct GruScope {
+  bool saved;
+  explicit GruScope(bool on) : saved(g_gru_no_cluster) { g_gru_no_cluster = saved || on; }
+  ~GruScope() { g_gru_no_cluster = saved; }
+};
+constexpr int kMaxAttempts = 6;
+
+// every weight region of the context in a fixed order (api.hip)
+std::vector<WeightRegion*> all_regions(Ctx& c, uint64_t* hash);
+// pins the first layer (in launch order) whose activations left fp16 range; false: none of the resident models named one
+bool localize_overflow(Ctx& c);
+void reset_after_failure(Ctx& c);
+// completes every ticket in flight, oldest first (api_convert.hip)
+void drain_tickets(rvcx_ctx* h);
+
+// the attempts of one call (see above); gru_plain: start on the single-workgroup GRU kernel (a ticket's re-run)
+template <typename F>
+void run_attempts(Ctx* C, bool repeat, bool gru_plain, F&& body) {
+  {
+    const int last = repeat ? kMaxAttempts - 1 : 0;
+    for (int attempt = 0; attempt <= last; ++attempt) {
+      Fp32Scope fp32_scope(attempt > 0 && attempt == last);
+      GruScope gru_scope(gru_plain);
+      C->launch_seq = 0;
+      C->err_snapshot = false;
+      try {
+        body(C);
+      } catch (const GruTimeout&) {
+        if (!repeat || gru_plain) throw;
+        gru_plain = true;
+        C->gru_fallbacks++;
+        reset_after_failure(*C);
+        --attempt;
+        continue;
+      }
+      if (attempt < last && C->take_overflow()) {
+        C->fp32_reruns++;
+        if (!localize_overflow(*C)) attempt = last - 1;     // nobody to pin: everything on fp32 next
+        continue;
+      }
+      if (attempt > 0 && attempt == last) (void)C->take_overflow();   // producers of split tensors may have re-raised the bit
+      break;
+    }
+  }
+}
+
+template <typename F>
+int api_call(rvcx_ctx* ctxp, bool repeat, F&& body, bool drain = true) {
+  Ctx* C = ctxp ? &ctxp->c : nullptr;
+  CtxLock guard = lock_ctx(ctxp);
+  try {
+    if (!C) fail("null context");
+    RVCX_HIP(hipSetDevice(C->device));
+    // every entry point has the context to itself: tickets in flight complete first (they stay waitable).  The one
+    // exception is rvcx_resample_f64*, which brings its own memory and stream order (drain = false)
+    if (drain) drain_tickets(ctxp);
+    if (!repeat) C->arena_budget = 0;     // loads / unloads change what is free: convert_micro_batch probes again
+    run_attempts(C, repeat, false, body);
+    return 0;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    if (C) {
+      C->last_error = e.what();
+      reset_after_failure(*C);
+    }
+    (void)hipGetLastError();
+    return -1;
+  }
+}
+
+// Tuning / fault-injection hooks (rvcx_conv_override, rvcx_debug_inject, rvcx_bench_*) are process-wide levers a serving
+// process must never meet by accident: they are refused (-2) unless the process was started with RVCX_DEBUG=1
+// (read once; tests/conftest.py and tools/ set it).
+bool debug_hooks_enabled();
+#define REQUIRE_DEBUG(ctxp, name)                                                             \
+  if (!debug_hooks_enabled()) {                                                               \
+    g_last_error = name ": debug / tuning hook refused (start the process with RVCX_DEBUG=1)"; \
+    if ((ctxp) != nullptr) {                                                                  \
+      CtxLock dbg_guard_ = lock_ctx((rvcx_ctx*)(ctxp));                                       \
+      ((rvcx_ctx*)(ctxp))->c.last_error = g_last_error;                                       \
+    }                                                                                         \
+    return -2;                                                                                \
+  }
+
+#define API_BEGIN(ctxp) return api_call((ctxp), true, [&](Ctx* C) {
+#define API_BEGIN_ONCE(ctxp) return api_call((ctxp), false, [&](Ctx* C) {
+#define API_END });
+
+// copy n elements from host or device memory into the arena
+template <typename T>
+T* to_dev(Ctx& c, const T* p, size_t n) {
+  T* d = c.arena.alloc<T>(n);
+  RVCX_HIP(hipMemcpyAsync(d, p, n * sizeof(T), hipMemcpyDefault, c.stream));
+  return d;
+}
+
+// one row of Gaussian noise: the caller's own values (parity runs), or Philox(seed) from `counter` on
+inline void fill_noise(float* dst, const float* given, size_t n, uint64_t seed, uint64_t counter, hipStream_t s) {
+  if (given) RVCX_HIP(hipMemcpyAsync(dst, given, n * sizeof(float), hipMemcpyDefault, s));
+  else launch_randn(dst, n, seed, counter, s);
+}
+
+inline SynthModel& get_synth(Ctx& c, int id) {
+  if (id < 0 || id >= (int)c.synths.size() || !c.synths[id]) fail("synth model not loaded");
+  return *c.synths[id];
+}
+
+}  // namespace api
+}  // namespace rvcx

@@ -52,6 +52,15 @@ struct F0Extra {
   long dither_n = 0;
   int seed_offset = 0;
 };
+// what get_f0_device takes beyond VC.get_f0's own arguments (all optional)
+struct F0Opts {
+  long frames = 0;                              // frames written per item; 0: n / 160
+  const float* pitch = nullptr;                 // host, B: a semitone shift per item instead of params.pitch
+  const std::vector<double>* track = nullptr;   // f0-file track (f0_file_track), applied to every item
+  const F0Extra* extra = nullptr;               // B
+  const int* ns_host = nullptr;                 // B, rmvpe / crepe: ragged batch -- item b holds ns_host[b] <= n samples in its row
+  const std::function<void()>* mid = nullptr;   // called once the model's first launches are enqueued
+};
 // A conversion in two halves.  convert_enqueue plans the call and enqueues ALL of its device work; convert_finish runs once
 // the device has completed it and resolves the stage times.  convert_batch (the synchronous call) is one after the other
 // with the stream synchronisations in between; a ticket (rvcx_convert_submit) returns to its caller between the two.
@@ -86,6 +95,7 @@ const std::vector<std::vector<long>>& convert_state_cuts(const ConvertState& st)
 // VC.pipeline for a list of utterances: equal-length utterances run as micro-batches (B > 1 through every network).
 void convert_batch(Ctx& c, int model_id, std::vector<UttIO>& utts, const rvcx_params& p, float* stage_ms /*9 or null*/);
 int convert_micro_batch(Ctx& c, int model_id, long n, const rvcx_params& p);   // utterances per micro-batch at this length
+size_t arena_budget(Ctx& c);   // activation bytes the context may plan with (probed once per context state, on its own device)
 
 // F0 back-end selected by params.f0_method: throws unless its model is resident; workspace for B signals of n_pad samples
 void check_f0_backend(const Ctx& c, const rvcx_params& p);
@@ -93,11 +103,12 @@ size_t f0_arena_bytes(const Ctx& c, const rvcx_params& p, int B, long n_pad);
 int crepe_hop(const rvcx_params& p);
 void crepe_f0_device(Ctx& c, const float* x, long n, const rvcx_params& p, long p_len, const F0Extra* ex, float* f0raw,
                      hipStream_t s);   // VC.get_f0_crepe for one padded signal on the device          // "mangio-crepe" frame step: params.hop_length, 128 when unset
-// VC.get_f0 on device for B equal-length reflect-padded signals: coarse/f0 rows of out_stride elements
-// ns_host (optional, B ints, rmvpe only): ragged batch -- item b holds ns_host[b] <= n_pad padded samples in its row
-long get_f0_device(Ctx& c, const float* apad, long n_pad, const rvcx_params& p, int* coarse, float* f0,
-                   hipStream_t s, int B = 1, long out_stride = 0, const std::function<void()>* mid = nullptr,
-                   const F0Extra* extra = nullptr, const int* ns_host = nullptr);
+// VC.get_f0 on device for B equal-length reflect-padded signals (B, n): coarse / f0 rows `stride` elements apart
+void get_f0_device(Ctx& c, const float* x, int B, long n, const rvcx_params& p, int* coarse, float* f0, long stride,
+                   hipStream_t s, const F0Opts& o = {});
+// VC.vc's front for S items of one geometry: HuBERT -> retrieval blend -> upsample + protect mix into phone (S, E, T)
+void vc_front(Ctx& c, int E, int S, const float* wav, long n, int Th, int T, const float* pitchf, float index_rate,
+              float protect, float* phone, hipStream_t s, hipEvent_t after_hubert = nullptr);
 int bucket_frames();                                                   // class width of the ragged micro-batches (frames)
 long bucket_length(long n, const rvcx_params& p, const Geometry& g);   // length whose geometry an n-sample utterance runs with
 

@@ -570,36 +570,39 @@ long bucket_length(long n, const rvcx_params& p, const Geometry& g) {
   return (k + 1) * cf * 160 - 1 - 2 * g.t_pad;          // the longest clip whose padded frame count is (k + 1) cf - 1
 }
 
+// Activation budget of a context: RVCX_ARENA_GB if set; else 100 GB (64 x 30 s: micro-batches of 16 instead of 11, +1 %) but
+// never more than 70 % of what the device has FREE right now -- a second context on the same GPU, or a smaller GPU, must not
+// turn the default into an out-of-memory error (the arena only ever grows: what this context already holds counts as free).
+// The free-memory probe runs ONCE per context state (first use after a load / unload: api_call clears the cached value on
+// every non-repeating entry point), on the context's OWN device -- rvcx_micro_batch reaches this function without
+// api_call's hipSetDevice -- so that the micro-batch partition is a function of (inputs, resident models, environment), not
+// of what another context happened to hold at the moment of the call.  The 70 % rule is a heuristic against the obvious
+// failure (two contexts, a smaller GPU), not an out-of-memory guarantee: two contexts created together can each see the
+// same free bytes.
+size_t arena_budget(Ctx& c) {
+  const size_t budget = (size_t)(getenv("RVCX_ARENA_GB") ? atoi(getenv("RVCX_ARENA_GB")) : 100) << 30;
+  if (getenv("RVCX_ARENA_GB")) return budget;
+  if (c.arena_budget == 0) {
+    int cur = -1;
+    (void)hipGetDevice(&cur);
+    if (cur != c.device) (void)hipSetDevice(c.device);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) {
+      const size_t mine = c.arena.capacity() + c.arena_f0.capacity() + c.arena_hub.capacity() +
+                          c.slot[0].arena.capacity() + c.slot[1].arena.capacity();
+      c.arena_budget = std::max<size_t>(1, std::min(budget, (size_t)((double)(free_b + mine) * 0.7)));
+    } else {
+      c.arena_budget = budget;
+    }
+    if (cur >= 0 && cur != c.device) (void)hipSetDevice(cur);
+  }
+  return c.arena_budget;
+}
+
 int convert_micro_batch(Ctx& c, int model_id, long n, const rvcx_params& p) {
   // 16: the BiGRU cluster kernel's co-residency bound (2 directions x 16 items x 4 workgroups = 128); C5 +3 %, C3 +1 % over 8
   static const int env_max = getenv("RVCX_MAX_BATCH") ? std::max(1, atoi(getenv("RVCX_MAX_BATCH"))) : 16;
-  // Activation budget: RVCX_ARENA_GB if set; else 100 GB (64 x 30 s: micro-batches of 16 instead of 11, +1 %) but never
-  // more than 70 % of what the device has FREE right now -- a second context on the same GPU, or a smaller GPU, must not
-  // turn the default into an out-of-memory error (the arena only ever grows: what this context already holds counts as free).
-  // The free-memory probe runs ONCE per context state (first conversion after a load / unload: api_call clears the cached
-  // value on every non-repeating entry point), on the context's OWN device -- rvcx_micro_batch reaches this function
-  // without api_call's hipSetDevice -- so that the micro-batch partition is a function of (inputs, resident models,
-  // environment), not of what another context happened to hold at the moment of the call.  The 70 % rule is a heuristic
-  // against the obvious failure (two contexts, a smaller GPU), not an out-of-memory guarantee: two contexts created
-  // together can each see the same free bytes.
-  size_t budget = (size_t)(getenv("RVCX_ARENA_GB") ? atoi(getenv("RVCX_ARENA_GB")) : 100) << 30;
-  if (!getenv("RVCX_ARENA_GB")) {
-    if (c.arena_budget == 0) {
-      int cur = -1;
-      (void)hipGetDevice(&cur);
-      if (cur != c.device) (void)hipSetDevice(c.device);
-      size_t free_b = 0, total_b = 0;
-      if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b > 0) {
-        const size_t mine = c.arena.capacity() + c.arena_f0.capacity() + c.arena_hub.capacity() +
-                            c.slot[0].arena.capacity() + c.slot[1].arena.capacity();
-        c.arena_budget = std::max<size_t>(1, std::min(budget, (size_t)((double)(free_b + mine) * 0.7)));
-      } else {
-        c.arena_budget = budget;
-      }
-      if (cur >= 0 && cur != c.device) (void)hipSetDevice(cur);
-    }
-    budget = c.arena_budget;
-  }
+  const size_t budget = arena_budget(c);
   const size_t per = convert_item_bytes(c, model_id, n, p) + f0_arena_bytes(c, p, 1, n + 32000L * p.x_pad);
   return (int)std::max<size_t>(1, std::min<size_t>((size_t)env_max, budget / std::max<size_t>(per, 1)));
 }
@@ -658,36 +661,81 @@ void crepe_f0_device(Ctx& c, const float* x, long n, const rvcx_params& p, long 
   launch_crepe_resize(pitch, F, p_len, f0raw, s);
 }
 
-long get_f0_device(Ctx& c, const float* apad, long n_pad, const rvcx_params& p, int* coarse, float* f0,
-                   hipStream_t s, int B, long out_stride, const std::function<void()>* mid, const F0Extra* extra,
-                   const int* ns_host) {
-  // VC.get_f0 (pipeline.py:132-201) on already reflect-padded signals (B, n_pad); coarse / f0 rows of out_stride
-  const long F = 1 + n_pad / 160, p_len = n_pad / 160;
+// VC.get_f0 (pipeline.py:132-201) on B already reflect-padded signals (B, n): model forward, pitch shift + coarse
+// quantisation, f0-file override; coarse / f0 rows are `stride` elements apart.  Frames written per item: o.frames, else
+// n / 160 (a ragged item: ns_host[b] / 160).  rmvpe's raw track has 1 + n / 160 frames whatever is kept of it; fcpe resizes
+// its track to the frame count (compute_f0(x, p_len)); mangio-crepe runs one item at a time at its own length.
+void get_f0_device(Ctx& c, const float* x, int B, long n, const rvcx_params& p, int* coarse, float* f0, long stride,
+                   hipStream_t s, const F0Opts& o) {
+  const long F = 1 + n / 160, p_len = o.frames ? o.frames : n / 160;
   check_f0_backend(c, p);
-  RVCX_CHECK(!ns_host || p.f0_method != RVCX_F0_FCPE, "get_f0: ragged batches are an rmvpe / mangio-crepe feature");
-  float* f0raw = c.arena.alloc<float>((size_t)B * F);
+  RVCX_CHECK(!o.ns_host || p.f0_method != RVCX_F0_FCPE, "get_f0: ragged batches are an rmvpe / mangio-crepe feature");
+  float* f0raw = c.arena.alloc<float>((size_t)B * std::max(F, p_len));
+  auto pitch_of = [&](int b) { return o.pitch ? (double)o.pitch[b] : p.pitch; };
+  auto frames_of = [&](int b) { return (int)(o.ns_host && !o.frames ? o.ns_host[b] / 160 : p_len); };
   if (p.f0_method == RVCX_F0_CREPE) {   // pipeline.py:151-152: get_f0_crepe(x, f0_min, f0_max, p_len, hop_length)
-    if (mid) (*mid)();
-    for (int b = 0; b < B; ++b) {      // one item at a time, each at ITS OWN length (rows stay n_pad apart)
+    if (o.mid) (*o.mid)();
+    for (int b = 0; b < B; ++b) {      // one item at a time, each at ITS OWN length (rows stay n apart)
       const size_t mark = c.arena.mark();
-      const long nb = ns_host ? ns_host[b] : n_pad, pl = nb / 160;
-      crepe_f0_device(c, apad + (size_t)b * n_pad, nb, p, pl, extra ? extra + b : nullptr, f0raw + (size_t)b * F, s);
+      crepe_f0_device(c, x + (size_t)b * n, o.ns_host ? o.ns_host[b] : n, p, frames_of(b), o.extra ? o.extra + b : nullptr,
+                      f0raw + (size_t)b * F, s);
       c.arena.reset(mark);
-      launch_f0_coarse(f0raw + (size_t)b * F, f0 + (size_t)b * out_stride, coarse + (size_t)b * out_stride, (int)pl,
-                       p.pitch, p.f0_min, p.f0_max, s);
+      launch_f0_coarse(f0raw + (size_t)b * F, f0 + (size_t)b * stride, coarse + (size_t)b * stride, frames_of(b), pitch_of(b),
+                       p.f0_min, p.f0_max, s);
     }
-    return p_len;
+  } else if (p.f0_method == RVCX_F0_FCPE) {   // pipeline.py:169-181: threshold 0.03, compute_f0(x, p_len)
+    fcpe_forward(c, *c.fcpe, B, x, n, 0.03f, f0raw, nullptr, nullptr, s, o.mid);
+    const int passes = o.pitch ? B : 1, per = B / passes;      // a shift per item: one post pass each
+    for (int b = 0; b < passes; ++b)
+      fcpe_post_coarse(c, f0raw + (size_t)b * F, per, (int)F, (int)p_len, f0 + (size_t)b * stride, coarse + (size_t)b * stride,
+                       stride, pitch_of(b), p.f0_min, p.f0_max, s);
+  } else {
+    rmvpe_forward(c, *c.rmvpe, B, x, n, 0.03f, p.f0_min, p.f0_max, f0raw, nullptr, s, nullptr, o.mid, o.ns_host);
+    for (int b = 0; b < B; ++b)
+      launch_f0_coarse(f0raw + (size_t)b * F, f0 + (size_t)b * stride, coarse + (size_t)b * stride, frames_of(b), pitch_of(b),
+                       p.f0_min, p.f0_max, s);
   }
-  if (p.f0_method == RVCX_F0_FCPE) {   // pipeline.py:169-181: threshold 0.03, compute_f0(x, p_len)
-    fcpe_forward(c, *c.fcpe, B, apad, n_pad, 0.03f, f0raw, nullptr, nullptr, s, mid);
-    fcpe_post_coarse(c, f0raw, B, (int)F, (int)p_len, f0, coarse, out_stride, p.pitch, p.f0_min, p.f0_max, s);
-    return p_len;
+  if (o.track && !o.track->empty()) {      // the f0 file replaces frames from x_pad seconds on (pipeline.py:185-191)
+    double* rep = c.arena.alloc<double>(o.track->size());
+    RVCX_HIP(hipMemcpyAsync(rep, o.track->data(), o.track->size() * 8, hipMemcpyHostToDevice, s));
+    for (int b = 0; b < B; ++b)
+      launch_f0_override(rep, (int)o.track->size(), 100 * p.x_pad, f0 + (size_t)b * stride, coarse + (size_t)b * stride,
+                         frames_of(b), p.f0_min, p.f0_max, s);
   }
-  rmvpe_forward(c, *c.rmvpe, B, apad, n_pad, 0.03f, p.f0_min, p.f0_max, f0raw, nullptr, s, nullptr, mid, ns_host);
-  for (int b = 0; b < B; ++b)
-    launch_f0_coarse(f0raw + (size_t)b * F, f0 + (size_t)b * out_stride, coarse + (size_t)b * out_stride,
-                     (int)(ns_host ? ns_host[b] / 160 : p_len), p.pitch, p.f0_min, p.f0_max, s);
-  return p_len;
+}
+
+// VC.vc's front (pipeline.py:203-262) for S items of one geometry: HuBERT features (E, Th) of every n-sample row of `wav`,
+// retrieval blend per item, x2 upsample + protect mix against pitchf (S, T) into phone (S, E, T).  Everything on `s`; scratch
+// comes from the arena and is given back.  after_hubert (optional) is recorded between HuBERT and the blend.
+void vc_front(Ctx& c, int E, int S, const float* wav, long n, int Th, int T, const float* pitchf, float index_rate,
+              float protect, float* phone, hipStream_t s, hipEvent_t after_hubert) {
+  Arena& A = c.arena;
+  const bool use_index = c.index && index_rate != 0.f, use_protect = protect < 0.5f;
+  const size_t mk0 = A.mark(), nf = (size_t)E * Th;
+  float* feats = A.alloc<float>(S * nf);
+  {
+    const size_t mk = A.mark();
+    hubert_features_for(c, *c.hubert, E, S, wav, n, feats, s);     // v2: layer 12; v1: final_proj(layer 9)
+    A.reset(mk);
+  }
+  if (after_hubert) RVCX_HIP(hipEventRecord(after_hubert, s));
+  const float* feats0 = feats;
+  if (use_index) {
+    if (use_protect) {
+      float* keep = A.alloc<float>(S * nf);
+      RVCX_HIP(hipMemcpyAsync(keep, feats, S * nf * 4, hipMemcpyDeviceToDevice, s));
+      feats0 = keep;
+    }
+    for (int i = 0; i < S; ++i) {
+      const size_t mk = A.mark();
+      index_blend(c, *c.index, feats + i * nf, Th, index_rate, nullptr, nullptr, s);
+      A.reset(mk);
+    }
+  }
+  for (int i = 0; i < S; ++i)
+    launch_upsample_protect(feats + i * nf, feats0 + i * nf, pitchf + (size_t)i * T, phone + (size_t)i * E * T, E, Th, T,
+                            protect, use_protect ? 1 : 0, s);
+  A.reset(mk0);      // (stream order: whatever reuses this memory on `s` runs behind these launches)
 }
 
 // VC.pipeline for a list of utterances (pipeline.py:289-467).
@@ -1017,8 +1065,11 @@ ConvertStatePtr convert_enqueue(Ctx& c, int model_id, std::vector<UttIO>& ios, c
       }
       std::vector<int> nsp(mb.count);
       for (int b = 0; b < mb.count; ++b) nsp[b] = (int)utts[order[mb.first + b]].n_pad;
-      get_f0_device(c, f.apad, n_pad, p, f.coarse, f.f0, sf, mb.count, n_pad / 160 + 8, mid, fx.data(),
-                    mb.ragged ? nsp.data() : nullptr);
+      F0Opts o;
+      o.extra = fx.data();
+      o.ns_host = mb.ragged ? nsp.data() : nullptr;
+      o.mid = mid;
+      get_f0_device(c, f.apad, mb.count, n_pad, p, f.coarse, f.f0, n_pad / 160 + 8, sf, o);
     } catch (...) {
       c.arena.swap(c.arena_f0);
       throw;
@@ -1251,7 +1302,7 @@ ConvertStatePtr convert_enqueue(Ctx& c, int model_id, std::vector<UttIO>& ios, c
       const int h1 = clk.mark(s);
       float* feats = fr[k & 1].feats + P.feats_off[gi];
       const float* feats0 = feats;
-      if (use_index) {
+      if (use_index) {      // vc_front's blend and mix, for members of their own Th / T inside the group's geometry
         if (use_protect) {
           float* keep = A.alloc<float>((size_t)G * E * Th);
           RVCX_HIP(hipMemcpyAsync(keep, feats, (size_t)G * E * Th * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -15,7 +15,7 @@ GOLD = os.path.join(os.path.dirname(__file__), "golden")
 def test_two_threads_share_one_context_through_the_mirror(tmp_path):
     """The reference builds fresh model objects per request (rvc/scripts/voice_conversion.py:71-100), so two Gradio
     worker threads never share state there.  Here every thread of the process gets the ONE resident context and ctypes
-    releases the GIL: every C entry point takes the context's mutex (csrc/api.hip) and the mirror holds the context's lock
+    releases the GIL: every C entry point takes the context's mutex (csrc/api_internal.h) and the mirror holds the context's lock
     around its call sequences.  Two threads x 4 requests on one context -- different clips, different index files (so
     "make the index resident, then convert" must not interleave), one thread also asking for the F0 track -- give, bit for
     bit, what each request gives alone; no error is left on the context."""
