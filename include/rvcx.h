@@ -538,6 +538,42 @@ int rvcx_op_layernorm_tm(rvcx_ctx*, const float* x, const float* gamma, const fl
 /* LayerNorm over channels of (B,C,T) */
 int rvcx_op_layernorm_c(rvcx_ctx*, const float* x, const float* gamma, const float* beta, float* y,
                         int B, int C, int T, float eps);
+/* GroupNorm(C, C) + GELU (erf) over time of x (B, C, T); lens (B) or NULL: statistics over an item's first lens[b] frames,
+ * zeros behind them.  y (B, C, T).  stats (B, C, 2) = {mean, rstd} and y_split (B, C, T: the split-fp16 image the next
+ * conv reads, decoded to fp32 = hi + lo / 256) come from the statistics + split-store pair; both or neither, C % 16 == 0. */
+int rvcx_op_groupnorm_gelu(rvcx_ctx*, const float* x, const float* gamma, const float* beta, int B, int C, int T, float eps,
+                           const int32_t* lens, float* y, float* stats, float* y_split);
+/* HuBERT's first extractor layer: conv1d(wav (B, n), w (C, 1, K), stride, no bias) -> GroupNorm(C, C) -> GELU -> split image,
+ * T0 = (n - K) / stride + 1 frames, lens (B) or NULL as above.  fused = 1: the form that never stores the fp32 map; fused = 0:
+ * conv, statistics, split store.  stats (B, C, 2); y_split (B, C, T0) decoded; raw_split (B C T0 2 halves, or NULL): the
+ * image's own bytes.  C % 16 == 0, K <= 16. */
+int rvcx_op_hubert_conv0(rvcx_ctx*, const float* wav, const float* w, const float* gamma, const float* beta, int B, int C,
+                         int n, int K, int stride, float eps, const int32_t* lens, int fused, float* stats, float* y_split,
+                         uint16_t* raw_split);
+/* NSF harmonic source: f0 (B, T) Hz, noise (B, T upp), lin_wb = {w, b} of the 1 -> 1 Linear -> har (B, T upp); frames behind
+ * lens[b] (or NULL) are zero */
+int rvcx_op_sine_source(rvcx_ctx*, const float* f0, const float* noise, const float* lin_wb, int B, int T, int upp, float sr,
+                        const int32_t* lens, float* har);
+/* n standard normal values: Philox4x32-10, counter (offset + i / 4, 0x52564358, 0), key = seed, Box-Muller on word pairs */
+int rvcx_op_randn(rvcx_ctx*, int64_t n, uint64_t seed, uint64_t offset, float* out);
+/* np.pad(x[b, :ns[b]], p, "reflect") for any p: x (B, n) -> y (B, n + 2 p), zeros behind ns[b] + 2 p; ns (B) or NULL */
+int rvcx_op_reflect_pad(rvcx_ctx*, const float* x, int B, int n, int p, const int32_t* ns, float* y);
+/* log(max(mel, 1e-5)) * bn[0] + bn[1]: mel (B, nmel, F) -> out (B, Tp, nmel + 2) with zero pad columns; item b has fs[b]
+ * frames reflected up to tps[b] rows, zero rows behind them (fs / tps (B) or NULL: F / Tp) */
+int rvcx_op_mel_post(rvcx_ctx*, const float* mel, int B, int nmel, int F, int Tp, const float* bn, const int32_t* fs,
+                     const int32_t* tps, float* out);
+/* salience (B, T, 360) in rows of ld floats -> f0 (B, T) Hz: local average of cents around the first maximum, 0 at or
+ * below thred and outside [f0_min, f0_max] */
+int rvcx_op_decode_f0(rvcx_ctx*, const float* sal, int B, int T, int ld, float thred, float f0_min, float f0_max, float* f0);
+/* 2 x 2 average pool of row-padded planes (H, Wp), x_ps floats apart -> (H / 2, (Wp - 2) / 2 + 2), y_ps apart; x holds
+ * planes * x_ps floats, y planes * y_ps (what the kernel leaves unwritten comes back NaN) */
+int rvcx_op_avgpool2(rvcx_ctx*, const float* x, int planes, int H, int Wp, int64_t x_ps, int64_t y_ps, float* y);
+/* row-padded (B, C, T, Wp) -> (B, C (Wp - 2), T) */
+int rvcx_op_gru_input(rvcx_ctx*, const float* x, int B, int C, int T, int Wp, float* y);
+/* nearest x2 upsampling of feats (C rows of ld_in floats, Th used) cropped to p_len, mixed with feats0 where pitchf < 1
+ * (use_protect) -> out (C rows of ld_out floats; what the kernel leaves unwritten comes back NaN) */
+int rvcx_op_upsample_protect(rvcx_ctx*, const float* feats, const float* feats0, const float* pitchf, int C, int Th, int p_len,
+                             float protect, int use_protect, int ld_in, int ld_out, float* out);
 /* bidirectional GRU: x (B,T,I) -> y (B,T,2H); weights in torch layout */
 int rvcx_op_bigru(rvcx_ctx*, const float* x, const float* w_ih, const float* w_hh, const float* b_ih,
                   const float* b_hh, const float* w_ih_r, const float* w_hh_r, const float* b_ih_r,

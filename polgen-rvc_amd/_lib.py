@@ -120,6 +120,8 @@ SYMBOLS = [
     "rvcx_convert_submit", "rvcx_convert_wait", "rvcx_convert_poll", "rvcx_convert_inflight", "rvcx_ticket_lead_ms",
     "rvcx_synth_infer_head", "rvcx_op_sola", "rvcx_stream_open", "rvcx_stream_step", "rvcx_stream_reset", "rvcx_stream_close",
     "rvcx_stream_out_len", "rvcx_stream_noise_len", "rvcx_stream_frames",
+    "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
+    "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
 ]
 
@@ -169,6 +171,19 @@ def lib() -> C.CDLL:
         _lib.rvcx_stream_out_len.argtypes = [C.c_void_p, C.c_int]
         _lib.rvcx_stream_noise_len.argtypes = [C.c_void_p, C.c_int]
         _lib.rvcx_stream_frames.argtypes = [C.c_void_p, C.c_int]
+        fp, ip, vp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
+        _lib.rvcx_op_groupnorm_gelu.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, ip, fp, fp, fp]
+        _lib.rvcx_op_hubert_conv0.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, ip,
+                                              C.c_int, fp, fp, C.POINTER(C.c_uint16)]
+        _lib.rvcx_op_sine_source.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, ip, fp]
+        _lib.rvcx_op_randn.argtypes = [vp, C.c_int64, C.c_uint64, C.c_uint64, fp]
+        _lib.rvcx_op_reflect_pad.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, ip, fp]
+        _lib.rvcx_op_mel_post.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp, ip, ip, fp]
+        _lib.rvcx_op_decode_f0.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, fp]
+        _lib.rvcx_op_avgpool2.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, fp]
+        _lib.rvcx_op_gru_input.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
+        _lib.rvcx_op_upsample_protect.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
+                                                  C.c_int, fp]
     return _lib
 
 
@@ -588,6 +603,109 @@ class Context:
         self._ck(lib().rvcx_op_layernorm_c(self._h, _p(x), _p(f32(gamma)), _p(f32(beta)), _p(y), B, Cc, T,
                                            C.c_float(eps)), "op_layernorm_c")
         return y
+
+    def groupnorm_gelu(self, x, gamma, beta, eps=1e-5, lens=None, split=True):
+        """GroupNorm(C, C) + GELU of x (B, C, T): (y, stats (B, C, 2) = {mean, rstd}, y_split decoded); the last two are None
+        unless split (C a multiple of 16)"""
+        x = f32(x)
+        B, Cc, T = x.shape
+        y = np.empty_like(x)
+        split = bool(split) and Cc % 16 == 0
+        st = np.empty((B, Cc, 2), np.float32) if split else None
+        ys = np.empty_like(x) if split else None
+        li = i32(lens)
+        self._ck(lib().rvcx_op_groupnorm_gelu(self._h, _p(x), _p(f32(gamma)), _p(f32(beta)), B, Cc, T, eps,
+                                              _p(li, C.c_int32), _p(y), _p(st), _p(ys)), "op_groupnorm_gelu")
+        return y, st, ys
+
+    def hubert_conv0(self, wav, w, gamma, beta, stride=5, eps=1e-5, lens=None, fused=True):
+        """HuBERT's first layer, wav (B, n) and w (C, 1, K) -> (stats (B, C, 2), y_split decoded (B, C, T0), the split image's
+        raw halves (uint16)); fused: the form without the fp32 map, else conv + statistics + split store"""
+        wav, w = f32(wav), f32(w)
+        B, n = wav.shape
+        Cc, _, K = w.shape
+        T0 = (n - K) // stride + 1
+        st = np.empty((B, Cc, 2), np.float32)
+        ys = np.empty((B, Cc, T0), np.float32)
+        raw = np.empty(B * Cc * T0 * 2, np.uint16)
+        li = i32(lens)
+        self._ck(lib().rvcx_op_hubert_conv0(self._h, _p(wav), _p(w), _p(f32(gamma)), _p(f32(beta)), B, Cc, n, K, int(stride),
+                                            eps, _p(li, C.c_int32), 1 if fused else 0, _p(st), _p(ys), _p(raw, C.c_uint16)),
+                 "op_hubert_conv0")
+        return st, ys, raw
+
+    def sine_source(self, f0, noise, lin_wb, upp, sr, lens=None):
+        """NSF harmonic source: f0 (B, T), noise (B, T * upp), lin_wb (w, b) -> har (B, T * upp)"""
+        f0, noise, wb = f32(f0), f32(noise), f32(lin_wb)
+        B, T = f0.shape
+        assert noise.shape == (B, T * upp) and wb.shape == (2,)
+        har = np.empty_like(noise)
+        li = i32(lens)
+        self._ck(lib().rvcx_op_sine_source(self._h, _p(f0), _p(noise), _p(wb), B, T, int(upp), float(sr), _p(li, C.c_int32),
+                                           _p(har)), "op_sine_source")
+        return har
+
+    def randn(self, n, seed, offset=0):
+        """n values of the Philox noise stream `seed` from counter `offset` on (four values per counter step)"""
+        out = np.empty(int(n), np.float32)
+        self._ck(lib().rvcx_op_randn(self._h, int(n), int(seed), int(offset), _p(out)), "op_randn")
+        return out
+
+    def reflect_pad(self, x, p, ns=None):
+        x = f32(x)
+        B, n = x.shape
+        y = np.empty((B, n + 2 * int(p)), np.float32)
+        li = i32(ns)
+        self._ck(lib().rvcx_op_reflect_pad(self._h, _p(x), B, n, int(p), _p(li, C.c_int32), _p(y)), "op_reflect_pad")
+        return y
+
+    def mel_post(self, mel, Tp, bn, fs=None, tps=None):
+        """mel (B, nmel, F) -> row-padded log-mel (B, Tp, nmel + 2); bn = (scale, shift)"""
+        mel, bn = f32(mel), f32(bn)
+        B, nmel, F = mel.shape
+        out = np.empty((B, int(Tp), nmel + 2), np.float32)
+        fi, ti = i32(fs), i32(tps)
+        self._ck(lib().rvcx_op_mel_post(self._h, _p(mel), B, nmel, F, int(Tp), _p(bn), _p(fi, C.c_int32), _p(ti, C.c_int32),
+                                        _p(out)), "op_mel_post")
+        return out
+
+    def decode_f0(self, sal, thred=0.03, f0_min=50.0, f0_max=1100.0):
+        """salience (B, T, ld >= 360; the first 360 columns count) -> f0 (B, T)"""
+        sal = f32(sal)
+        B, T, ld = sal.shape
+        f0 = np.empty((B, T), np.float32)
+        self._ck(lib().rvcx_op_decode_f0(self._h, _p(sal), B, T, ld, thred, f0_min, f0_max, _p(f0)), "op_decode_f0")
+        return f0
+
+    def avgpool2(self, x, H, Wp, y_ps=None):
+        """x (planes, x_ps >= H * Wp): row-padded planes -> (planes, y_ps) holding (H // 2, (Wp - 2) // 2 + 2) planes"""
+        x = f32(x)
+        planes, x_ps = x.shape
+        dense = (H // 2) * ((Wp - 2) // 2 + 2)
+        y_ps = dense if y_ps is None else int(y_ps)
+        y = np.empty((planes, y_ps), np.float32)
+        self._ck(lib().rvcx_op_avgpool2(self._h, _p(x), planes, int(H), int(Wp), x_ps, y_ps, _p(y)), "op_avgpool2")
+        return y
+
+    def gru_input(self, x):
+        """row-padded (B, C, T, Wp) -> (B, C * (Wp - 2), T)"""
+        x = f32(x)
+        B, Cc, T, Wp = x.shape
+        y = np.empty((B, Cc * (Wp - 2), T), np.float32)
+        self._ck(lib().rvcx_op_gru_input(self._h, _p(x), B, Cc, T, Wp, _p(y)), "op_gru_input")
+        return y
+
+    def upsample_protect(self, feats, feats0, pitchf, Th, p_len, protect=0.33, use_protect=True, ld_out=None):
+        """feats / feats0 (C, ld_in >= Th), pitchf (p_len) -> out (C, ld_out >= p_len)"""
+        feats = f32(feats)
+        Cc, ld_in = feats.shape
+        feats0 = None if feats0 is None else f32(feats0)
+        pitchf = None if pitchf is None else f32(pitchf)
+        ld_out = int(p_len) if ld_out is None else int(ld_out)
+        out = np.empty((Cc, ld_out), np.float32)
+        self._ck(lib().rvcx_op_upsample_protect(self._h, _p(feats), _p(feats0), _p(pitchf), Cc, int(Th), int(p_len), protect,
+                                                1 if use_protect else 0, ld_in, ld_out, _p(out)), "op_upsample_protect")
+        return out
 
     # ---- models -----------------------------------------------------------------------
     def load_synth(self, cfg_struct, state: dict) -> int:

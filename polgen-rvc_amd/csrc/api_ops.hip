@@ -1,5 +1,6 @@
 // C ABI of librvcx.so (include/rvcx.h): kernel-level entry points of the tests and the tuning tools (rvcx_op_*, rvcx_bench_*).
 #include "api_internal.h"
+#include "h3_device.h"
 
 using namespace rvcx;
 using namespace rvcx::api;
@@ -477,6 +478,19 @@ static void decode_xs(const std::vector<uint16_t>& raw, long rows, int Cc, float
     }
 }
 
+// host view of a channel-first split image (ops.hip, groupnorm_gelu_split_kernel): per item XS[c/16][op][(c%16)/8][t][8]
+// halves, op 0 = hi, op 1 = lo * kH3Scale (h3_device.h)
+static void decode_split_cf(const std::vector<uint16_t>& raw, int B, int Cc, int T, float* out) {
+  for (int b = 0; b < B; ++b)
+    for (int c = 0; c < Cc; ++c)
+      for (int t = 0; t < T; ++t) {
+        const size_t item = (size_t)b * Cc * T * 2;
+        const size_t hi = item + ((size_t)(((c >> 4) * 2 + 0) * 2 + ((c >> 3) & 1)) * T + t) * 8 + (c & 7);
+        const size_t lo = item + ((size_t)(((c >> 4) * 2 + 1) * 2 + ((c >> 3) & 1)) * T + t) * 8 + (c & 7);
+        out[((size_t)b * Cc + c) * T + t] = half_to_float(raw[hi]) + half_to_float(raw[lo]) / kH3Scale;
+      }
+}
+
 int rvcx_op_gemm_tm(rvcx_ctx* ctx, const float* x_cf, const float* w, const float* bias, const float* res_tm, int B,
                     int T, int Cin, int Cout, int act, int exact_fp32, float* y_tm, float* y_cf, float* y_split) {
   API_BEGIN(ctx)
@@ -584,6 +598,243 @@ int rvcx_op_layernorm_c(rvcx_ctx* ctx, const float* x, const float* gamma, const
   float* dy = C->arena.alloc<float>(n);
   launch_layernorm_c(dx, to_dev(*C, gamma, Cc), to_dev(*C, beta, Cc), dy, B, Cc, T, eps, nullptr, C->stream);
   to_host(*C, y, dy, n);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_groupnorm_gelu(rvcx_ctx* ctx, const float* x, const float* gamma, const float* beta, int B, int Cc, int T, float eps,
+                           const int32_t* lens, float* y, float* stats, float* y_split) {
+  API_BEGIN(ctx)
+  if (!x || !gamma || !beta || !y || B <= 0 || Cc <= 0 || T <= 0) fail("op_groupnorm_gelu: bad argument");
+  if ((stats == nullptr) != (y_split == nullptr)) fail("op_groupnorm_gelu: stats and y_split come together");
+  if (lens)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > T) fail("op_groupnorm_gelu: lens outside [1, T]");
+  const size_t n = (size_t)B * Cc * T;
+  C->arena.reserve(n * 4 * 3 + (size_t)B * Cc * 8 + (64 << 20));
+  C->arena.reset();
+  hipStream_t s = C->stream;
+  float* dx = to_dev(*C, x, n);
+  const float *dg = to_dev(*C, gamma, Cc), *db = to_dev(*C, beta, Cc);
+  const int* dl = (lens ? to_dev(*C, lens, B) : nullptr);
+  float* dy = C->arena.alloc<float>(n);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, n * 4, s));      // NaN fill: every element must be written
+  launch_groupnorm_gelu(dx, dg, db, dy, B, Cc, T, eps, s, dl);
+  float *dst = nullptr, *ds = nullptr;
+  if (stats) {
+    dst = C->arena.alloc<float>((size_t)B * Cc * 2);
+    ds = C->arena.alloc<float>(n);
+    RVCX_HIP(hipMemsetAsync(dst, 0xff, (size_t)B * Cc * 8, s));
+    RVCX_HIP(hipMemsetAsync(ds, 0xff, n * 4, s));
+    launch_groupnorm_gelu_split(dx, dg, db, dst, ds, B, Cc, T, eps, s, dl, C->dev_err, nullptr, 0);
+  }
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, y, dy, n);
+  if (stats) {
+    to_host(*C, stats, dst, (size_t)B * Cc * 2);
+    std::vector<uint16_t> raw(n * 2);
+    RVCX_HIP(hipMemcpy(raw.data(), ds, raw.size() * 2, hipMemcpyDeviceToHost));
+    decode_split_cf(raw, B, Cc, T, y_split);
+  }
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_hubert_conv0(rvcx_ctx* ctx, const float* wav, const float* w, const float* gamma, const float* beta, int B, int Cc,
+                         int n, int K, int stride, float eps, const int32_t* lens, int fused, float* stats, float* y_split,
+                         uint16_t* raw_split) {
+  API_BEGIN(ctx)
+  TEMP_REGION(C);
+  if (!wav || !w || !gamma || !beta || !stats || !y_split || B <= 0 || Cc <= 0 || K <= 0 || stride <= 0 || n < K)
+    fail("op_hubert_conv0: bad argument");
+  const int T0 = (n - K) / stride + 1;
+  if (lens)
+    for (int b = 0; b < B; ++b)
+      if (lens[b] < 1 || lens[b] > T0) fail("op_hubert_conv0: lens outside [1, T0]");
+  const size_t ny = (size_t)B * Cc * T0;
+  C->arena.reserve(((size_t)B * n + 2 * ny + (size_t)B * Cc * 2) * 4 + (64 << 20));
+  C->arena.reset();
+  hipStream_t s = C->stream;
+  ConvW L = make_conv(*C, w, nullptr, Cc, 1, K, 1);
+  float* dw = to_dev(*C, wav, (size_t)B * n);
+  const float *dg = to_dev(*C, gamma, Cc), *db = to_dev(*C, beta, Cc);
+  const int* dl = (lens ? to_dev(*C, lens, B) : nullptr);
+  float* dst = C->arena.alloc<float>((size_t)B * Cc * 2);
+  float* ds = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dst, 0xff, (size_t)B * Cc * 8, s));      // NaN fill: every element must be written
+  RVCX_HIP(hipMemsetAsync(ds, 0xff, ny * 4, s));
+  if (fused) {
+    launch_hubert_conv0_gn_gelu_split(dw, (long)n, L.w, K, stride, L.cin_gp * L.cout_gp, dg, db, nullptr, dst, ds, B, Cc, T0, eps,
+                                      s, dl, C->dev_err, nullptr, 0);
+  } else {      // hubert.hip's three passes: the conv stores the fp32 map, statistics, split store
+    float* dm = C->arena.alloc<float>(ny);
+    RVCX_HIP(hipMemsetAsync(dm, 0xff, ny * 4, s));
+    ConvArgs a = conv1d_args(L, dw, dm, B, n, T0, stride, 1, 0);
+    a.lens_out = dl;
+    C->conv(a);
+    launch_groupnorm_gelu_split(dm, dg, db, dst, ds, B, Cc, T0, eps, s, dl, C->dev_err, nullptr, 0);
+  }
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, stats, dst, (size_t)B * Cc * 2);
+  std::vector<uint16_t> raw(ny * 2);
+  RVCX_HIP(hipMemcpy(raw.data(), ds, raw.size() * 2, hipMemcpyDeviceToHost));
+  decode_split_cf(raw, B, Cc, T0, y_split);
+  if (raw_split) std::memcpy(raw_split, raw.data(), raw.size() * 2);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_sine_source(rvcx_ctx* ctx, const float* f0, const float* noise, const float* lin_wb, int B, int T, int upp, float sr,
+                        const int32_t* lens, float* har) {
+  API_BEGIN(ctx)
+  if (!f0 || !noise || !lin_wb || !har || B <= 0 || T <= 0 || upp <= 0) fail("op_sine_source: bad argument");
+  const size_t n = (size_t)B * T * upp;
+  C->arena.reserve(n * 8 + (size_t)B * T * 24 + (64 << 20));
+  C->arena.reset();
+  hipStream_t s = C->stream;
+  const float* df = to_dev(*C, f0, (size_t)B * T);
+  const float* dn = to_dev(*C, noise, n);
+  const float* dwb = to_dev(*C, lin_wb, 2);
+  const int* dl = (lens ? to_dev(*C, lens, B) : nullptr);
+  double* sc = C->arena.alloc<double>((size_t)B * T * 2);      // prefixes (fp64) + rad (fp32), as synth.hip sizes it
+  float* dh = C->arena.alloc<float>(n);
+  RVCX_HIP(hipMemsetAsync(dh, 0xff, n * 4, s));      // NaN fill: every element must be written
+  launch_sine_source(df, dn, dh, B, T, upp, sr, dwb, dl, sc, s);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, har, dh, n);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_randn(rvcx_ctx* ctx, int64_t n, uint64_t seed, uint64_t offset, float* out) {
+  API_BEGIN(ctx)
+  if (!out || n <= 0) fail("op_randn: bad argument");
+  C->arena.reserve((size_t)n * 4 + (64 << 20));
+  C->arena.reset();
+  float* d = C->arena.alloc<float>((size_t)n + 4);
+  RVCX_HIP(hipMemsetAsync(d, 0xff, ((size_t)n + 4) * 4, C->stream));      // NaN fill, and four guard words behind the tail
+  launch_randn(d, (size_t)n, seed, offset, C->stream);
+  RVCX_HIP(hipGetLastError());
+  std::vector<float> h((size_t)n + 4);
+  to_host(*C, h.data(), d, h.size());
+  for (size_t i = (size_t)n; i < h.size(); ++i)
+    if (!std::isnan(h[i])) fail("op_randn: wrote behind the last value");
+  std::memcpy(out, h.data(), (size_t)n * 4);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_reflect_pad(rvcx_ctx* ctx, const float* x, int B, int n, int p, const int32_t* ns, float* y) {
+  API_BEGIN(ctx)
+  if (!x || !y || B <= 0 || n <= 0 || p < 0) fail("op_reflect_pad: bad argument");
+  if (ns)
+    for (int b = 0; b < B; ++b)
+      if (ns[b] < 1 || ns[b] > n) fail("op_reflect_pad: ns outside [1, n]");
+  const size_t ny = (size_t)B * (n + 2 * p);
+  C->arena.reserve(((size_t)B * n + ny) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* dx = to_dev(*C, x, (size_t)B * n);
+  const int* dn = (ns ? to_dev(*C, ns, B) : nullptr);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: every element must be written
+  launch_reflect_pad(dx, dy, B, n, p, (long)n + 2 * p, C->stream, dn);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, y, dy, ny);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_mel_post(rvcx_ctx* ctx, const float* mel, int B, int nmel, int F, int Tp, const float* bn, const int32_t* fs,
+                     const int32_t* tps, float* out) {
+  API_BEGIN(ctx)
+  if (!mel || !bn || !out || B <= 0 || nmel <= 0 || F <= 0 || Tp <= 0) fail("op_mel_post: bad argument");
+  for (int b = 0; b < B; ++b) {
+    const int Fb = fs ? fs[b] : F, Tb = tps ? tps[b] : Tp;
+    if (Fb < 1 || Fb > F || Tb < 0 || Tb > Tp || Tb > 2 * Fb - 1) fail("op_mel_post: rows cannot be reflected from the item's frames");
+  }
+  const size_t nx = (size_t)B * nmel * F, ny = (size_t)B * Tp * (nmel + 2);
+  C->arena.reserve((nx + ny) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* dm = to_dev(*C, mel, nx);
+  const float* dbn = to_dev(*C, bn, 2);
+  const int* dfs = (fs ? to_dev(*C, fs, B) : nullptr);
+  const int* dtp = (tps ? to_dev(*C, tps, B) : nullptr);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: every element must be written
+  launch_mel_post(dm, dy, B, nmel, F, Tp, dbn, C->stream, dfs, dtp);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, out, dy, ny);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_decode_f0(rvcx_ctx* ctx, const float* sal, int B, int T, int ld, float thred, float f0_min, float f0_max, float* f0) {
+  API_BEGIN(ctx)
+  if (!sal || !f0 || B <= 0 || T <= 0 || ld < 360) fail("op_decode_f0: bad argument");
+  const size_t nx = (size_t)B * T * ld, ny = (size_t)B * T;
+  C->arena.reserve((nx + ny) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* dsal = to_dev(*C, sal, nx);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: every element must be written
+  launch_decode_f0(dsal, dy, B, T, ld, thred, f0_min, f0_max, C->stream);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, f0, dy, ny);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_avgpool2(rvcx_ctx* ctx, const float* x, int planes, int H, int Wp, int64_t x_ps, int64_t y_ps, float* y) {
+  API_BEGIN(ctx)
+  if (!x || !y || planes <= 0 || H < 2 || Wp < 4 || Wp % 2) fail("op_avgpool2: bad argument");
+  if (x_ps < (int64_t)H * Wp || y_ps < (int64_t)(H / 2) * ((Wp - 2) / 2 + 2)) fail("op_avgpool2: plane stride smaller than the plane");
+  const size_t nx = (size_t)planes * x_ps, ny = (size_t)planes * y_ps;
+  C->arena.reserve((nx + ny) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* dx = to_dev(*C, x, nx);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: what the kernel does not own stays NaN
+  launch_avgpool2(dx, dy, planes, H, Wp, (long)x_ps, (long)y_ps, C->stream);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, y, dy, ny);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_gru_input(rvcx_ctx* ctx, const float* x, int B, int Cc, int T, int Wp, float* y) {
+  API_BEGIN(ctx)
+  if (!x || !y || B <= 0 || Cc <= 0 || T <= 0 || Wp < 3) fail("op_gru_input: bad argument");
+  const size_t nx = (size_t)B * Cc * T * Wp, ny = (size_t)B * Cc * (Wp - 2) * T;
+  C->arena.reserve((nx + ny) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* dx = to_dev(*C, x, nx);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: every element must be written
+  launch_gru_input(dx, dy, B, Cc, T, Wp, C->stream);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, y, dy, ny);
+  C->arena.reset();
+  API_END
+}
+
+int rvcx_op_upsample_protect(rvcx_ctx* ctx, const float* feats, const float* feats0, const float* pitchf, int Cc, int Th, int p_len,
+                             float protect, int use_protect, int ld_in, int ld_out, float* out) {
+  API_BEGIN(ctx)
+  if (!feats || !out || Cc <= 0 || Th <= 0 || p_len <= 0 || p_len > 2 * Th) fail("op_upsample_protect: bad argument");
+  if (use_protect && (!feats0 || !pitchf)) fail("op_upsample_protect: protect needs feats0 and pitchf");
+  const int li = ld_in > 0 ? ld_in : Th, lo = ld_out > 0 ? ld_out : p_len;
+  if (li < Th || lo < p_len) fail("op_upsample_protect: row stride smaller than the row");
+  const size_t nx = (size_t)Cc * li, ny = (size_t)Cc * lo;
+  C->arena.reserve((2 * nx + ny + (size_t)p_len) * 4 + (64 << 20));
+  C->arena.reset();
+  const float* df = to_dev(*C, feats, nx);
+  const float* df0 = (use_protect ? to_dev(*C, feats0, nx) : nullptr);
+  const float* dp = (use_protect ? to_dev(*C, pitchf, (size_t)p_len) : nullptr);
+  float* dy = C->arena.alloc<float>(ny);
+  RVCX_HIP(hipMemsetAsync(dy, 0xff, ny * 4, C->stream));      // NaN fill: what the kernel does not own stays NaN
+  launch_upsample_protect(df, df0, dp, dy, Cc, Th, p_len, protect, use_protect, C->stream, ld_in, ld_out);
+  RVCX_HIP(hipGetLastError());
+  to_host(*C, out, dy, ny);
   C->arena.reset();
   API_END
 }
