@@ -380,8 +380,8 @@ int rvcx_vc_frames(rvcx_ctx*, int64_t n);
  * counterpart -- one frame (10 ms) of added latency, the clamp of pipeline.py:257-262.
  *
  * Deliberately absent, because they are whole-clip operations of VC.pipeline (pipeline.py:329, 450-461): the 48 Hz zero-phase
- * high-pass, the volume envelope, resample_sr and the peak normalisation.  Neither is there resampling: input is 16 kHz mono
- * float32; callers resample with rvcx_resample_f64, which runs beside other work.
+ * high-pass, the volume envelope, resample_sr and the peak normalisation.  A session opened with rvcx_stream_open takes 16 kHz
+ * mono float32 and returns the model's rate; rvcx_stream_open_io (below) puts a stateful resampler at either edge.
  *
  * Noise.  noise_hd[s] (parity): z_noise (inter * T) then src_noise ((Fb + Fx + Fs) * upp) for this step.  NULL: stream s draws
  * from Philox(p->seed + s) at counter offsets that no two steps share.  A reset zeroes ring, carry and step counter: a reset
@@ -400,12 +400,14 @@ typedef struct {
 int rvcx_stream_open(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_params* p, const int32_t* sid,
                      const float* pitch, int* stream_id);
 /* block16k_hd: S pointers to Fb * 160 samples; out_hd: S pointers to Fb * upp samples; pre_sola_hd (optional): S pointers to
- * (Fb + Fx + Fs) * upp samples, the synthesized tail before SOLA; offsets (optional, host): the S chosen SOLA offsets */
+ * (Fb + Fx + Fs) * upp samples, the synthesized tail before SOLA; offsets (optional, host): the S chosen SOLA offsets.
+ * Sessions opened with rvcx_stream_open_io: block16k_hd[s] holds rvcx_stream_in_len x in_channels floats and out_hd[s]
+ * rvcx_stream_out_len floats (see "live streams at the sound card's rate" below) */
 int rvcx_stream_step(rvcx_ctx*, int stream_id, const float* const* block16k_hd, const float* const* noise_hd,
                      float* const* out_hd, float* const* pre_sola_hd, int32_t* offsets);
 int rvcx_stream_reset(rvcx_ctx*, int stream_id);
 int rvcx_stream_close(rvcx_ctx*, int stream_id);
-int64_t rvcx_stream_out_len(rvcx_ctx*, int stream_id);   /* Fb * upp */
+int64_t rvcx_stream_out_len(rvcx_ctx*, int stream_id);   /* Fb * out_rate / 100 when the output is resampled, Fb * upp otherwise */
 int64_t rvcx_stream_noise_len(rvcx_ctx*, int stream_id); /* inter * T + (Fb + Fx + Fs) * upp per stream and step */
 int rvcx_stream_frames(rvcx_ctx*, int stream_id);        /* T, the frames the TextEncoder sees per step */
 /* SOLA (synchronised overlap-add) of one synthesized tail y (Lb + Lx + Ls samples) against the carry b_in (Lx samples):
@@ -418,9 +420,74 @@ int rvcx_stream_frames(rvcx_ctx*, int stream_id);        /* T, the frames the Te
 int rvcx_op_sola(rvcx_ctx*, const float* y_hd, const float* b_in_hd, int Lb, int Lx, int Ls, float* out_hd,
                  float* b_out_hd, int32_t* offset, float* scores_hd);
 
+/* ---- live streams at the sound card's rate ----------------------------------------------------------------------------
+ * rvcx_stream_open_io puts a stateful resampler in front of the ring (in_rate, in_channels -> 16 kHz mono) and one behind SOLA
+ * (the model's rate sr -> out_rate), both inside the step, on the device.
+ *
+ * Filter.  Always kaiser_hq (kind 0 of rvcx_resample_f64_kind: 96 zero crossings per wing, taps at exact table positions, left
+ * wing then right wing, the running sum in double, one rounding to float32).  RVCX_RESAMPLER does not apply to sessions.  The
+ * one-shot kernel and the session's kernel share one tap loop.
+ *
+ * Delay.  delay(sr_in, sr_out) = 0 for equal rates, else ceil(96 max(1, sr_out / sr_in)) output samples: with it every sample
+ * a step emits has all its taps inside the input received so far, so it equals the one-shot result on the complete signal
+ * bit for bit.  6.0 ms on the way in (96 samples at 16 kHz), 2.2 - 3.0 ms on the way out (96 samples at 44.1 kHz; 116 at 48 kHz
+ * from a 40 k model, 144 from a 32 k model).
+ *
+ * Input.  x = the mono mix (mean over channels, in double) of everything a stream has received since open or reset, u = the
+ * one-shot kaiser_hq resample of x to 16 kHz, u[t] = 0 for t < 0.  Step k = 0, 1, .. appends u[k Fb 160 - d_in + i], i = 0 ..
+ * Fb 160 - 1, to the ring, d_in = delay(in_rate, 16000).  Every sample is computed from its global index t (int64, restarting
+ * at 0 on reset) at position (double)t * (in_rate / 16000): the result does not depend on how the signal was cut into blocks.
+ * Output.  v = the concatenated SOLA blocks at the model's rate, w = its one-shot resample to out_rate; step k returns
+ * w[k Fb out_rate / 100 - d_out + i], i = 0 .. Fb out_rate / 100 - 1, d_out = delay(sr, out_rate); negative indices give 0.
+ *
+ * Rates.  in_rate and out_rate are multiples of 100 Hz within 8000 .. 192000 (a 10 ms frame is a whole number of samples);
+ * a rate below 8000 is accepted only beside a partner below 8000 (reduced-size voice models: 4800 Hz -> 6000 Hz).  Anything
+ * else -- 22050, 11025, 7900 in front of 16 kHz -- is refused at open.  in_rate 0 or 16000 with one channel, and out_rate 0 or
+ * sr, mean "none": that side is rvcx_stream_open's, launch for launch and bit for bit, delay 0.  Equal rates with several
+ * channels: the mono mix alone (rounded once to float32), delay 0.  The two sides are independent.
+ *
+ * State.  Per stream and side a FIFO of past samples at the side's input rate (mono-mixed on the way in; SOLA output on the way
+ * out), held in double, of ceil(d sr_in / sr_out) + ceil(96 / min(1, sr_out / sr_in)) + 2 frames of history plus the newest
+ * block; the global index is the session's step counter times the block.  FIFOs, the staged blocks and the filter tables are
+ * allocations of the session's own; FIFOs exist twice and change places with ring and carry once a step has succeeded.
+ * rvcx_stream_reset zeroes them.
+ *
+ * rvcx_stream_step keeps its signature: block16k_hd[s] holds rvcx_stream_in_len x in_channels floats (interleaved), out_hd[s]
+ * rvcx_stream_out_len floats; pre_sola_hd and offsets keep their meaning at the model's rate.  rvcx_last_timing keeps nine
+ * slots: the input resampler is counted in the first interval (with F0), the output resampler in the last ("SOLA + copies"). */
+typedef struct {
+  int32_t in_rate;      /* Hz; 0 or 16000 with in_channels 1: blocks are 16 kHz mono, today's path */
+  int32_t in_channels;  /* >= 1, interleaved (frames, channels); averaged like librosa.to_mono */
+  int32_t out_rate;     /* Hz; 0 or the voice model's rate: none */
+  int32_t reserved;
+} rvcx_stream_io;
+/* io == NULL: rvcx_stream_open */
+int rvcx_stream_open_io(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_stream_io*, const rvcx_params* p,
+                        const int32_t* sid, const float* pitch, int* stream_id);
+int64_t rvcx_stream_in_len(rvcx_ctx*, int stream_id);   /* frames per block and stream: Fb * in_rate / 100 (x in_channels floats) */
+/* in_delay_16k: samples at 16 kHz; out_delay: samples at out_rate; either may be NULL */
+int rvcx_stream_delays(rvcx_ctx*, int stream_id, int32_t* in_delay_16k, int32_t* out_delay);
+/* host only, no GPU: the definition above; -1 for rates open refuses */
+int rvcx_stream_resample_delay(int sr_in, int sr_out);
+/* taps of the LAST successful step (zeros before the first): in16k_hd, S pointers to the Fb * 160 samples that entered the
+ * rings; native_hd, S pointers to the Fb * upp samples of SOLA output in front of the output resampler -- kept only by sessions
+ * whose output is resampled (otherwise out_hd of the step is that block, and asking fails).  Either table may be NULL */
+int rvcx_stream_last_taps(rvcx_ctx*, int stream_id, float* const* in16k_hd, float* const* native_hd);
+/* live controls, applied from the next step on; pitch / sid: S values or NULL, index_rate / protect: NaN keeps the current
+ * value.  Ring, FIFOs, carry and the noise counters are untouched.  sid out of range, or index_rate != 0 with a resident index
+ * of the wrong width: -1, nothing changed */
+int rvcx_stream_set(rvcx_ctx*, int stream_id, const float* pitch, const int32_t* sid, float index_rate, float protect);
+/* the session's resampler without a session: S rows of `frames` input frames (x_hd: S x frames x channels, interleaved), cut
+ * into blocks of block_frames 10 ms frames (frames must be a multiple of block_frames * sr_in / 100), through the same FIFO +
+ * kernel code a session runs per step; y_hd receives S rows of frames * sr_out / sr_in samples, delayed as defined */
+int rvcx_op_stream_resample(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int channels, int sr_in, int sr_out,
+                            int block_frames, float* y_hd);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
- * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total} */
+ * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
+ * {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} -- a session's input resampler is counted in the
+ * F0 interval, its output resampler in "SOLA + copies" */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration

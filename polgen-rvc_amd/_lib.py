@@ -71,6 +71,17 @@ class UttExtra(C.Structure):
 F0_RMVPE, F0_FCPE, F0_CREPE = 0, 1, 2        # rvcx_params.f0_method
 
 
+class StreamIO(C.Structure):
+    """rvcx_stream_io: the rates at the two edges of a live-stream session (0: none on that side)"""
+    _fields_ = [("in_rate", C.c_int32), ("in_channels", C.c_int32), ("out_rate", C.c_int32), ("reserved", C.c_int32)]
+
+
+def stream_resample_delay(sr_in: int, sr_out: int) -> int:
+    """rvcx_stream_resample_delay (host only): the delay of a session's resampler in output samples, 0 for equal rates,
+    ceil(96 * max(1, sr_out / sr_in)) otherwise; -1 for rates a session refuses"""
+    return int(lib().rvcx_stream_resample_delay(int(sr_in), int(sr_out)))
+
+
 class StreamCfg(C.Structure):
     """rvcx_stream_cfg: the geometry of a live-stream session in 10 ms frames"""
     _fields_ = [("n_streams", C.c_int32), ("block_frames", C.c_int32), ("context_frames", C.c_int32),
@@ -120,6 +131,8 @@ SYMBOLS = [
     "rvcx_convert_submit", "rvcx_convert_wait", "rvcx_convert_poll", "rvcx_convert_inflight", "rvcx_ticket_lead_ms",
     "rvcx_synth_infer_head", "rvcx_op_sola", "rvcx_stream_open", "rvcx_stream_step", "rvcx_stream_reset", "rvcx_stream_close",
     "rvcx_stream_out_len", "rvcx_stream_noise_len", "rvcx_stream_frames",
+    "rvcx_stream_open_io", "rvcx_stream_in_len", "rvcx_stream_delays", "rvcx_stream_resample_delay", "rvcx_stream_last_taps",
+    "rvcx_stream_set", "rvcx_op_stream_resample",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
@@ -171,6 +184,12 @@ def lib() -> C.CDLL:
         _lib.rvcx_stream_out_len.argtypes = [C.c_void_p, C.c_int]
         _lib.rvcx_stream_noise_len.argtypes = [C.c_void_p, C.c_int]
         _lib.rvcx_stream_frames.argtypes = [C.c_void_p, C.c_int]
+        _lib.rvcx_stream_in_len.restype = C.c_int64
+        _lib.rvcx_stream_in_len.argtypes = [C.c_void_p, C.c_int]
+        _lib.rvcx_stream_resample_delay.argtypes = [C.c_int, C.c_int]
+        _lib.rvcx_stream_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float]
+        _lib.rvcx_op_stream_resample.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p]
         fp, ip, vp = C.POINTER(C.c_float), C.POINTER(C.c_int32), C.c_void_p
         _lib.rvcx_op_groupnorm_gelu.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, ip, fp, fp, fp]
         _lib.rvcx_op_hubert_conv0.argtypes = [vp, fp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, ip,
@@ -354,29 +373,43 @@ class Ticket:
 
 
 class StreamSession:
-    """S lock-step live streams (Context.stream_open).  step() takes one 16 kHz block per stream and returns the converted
-    blocks at the voice model's rate; the rolling context, the SOLA carry and the noise counters live on the device."""
+    """S lock-step live streams (Context.stream_open).  step() takes one block per stream -- 16 kHz mono, or in_rate x
+    in_channels when the session was opened with them -- and returns the converted blocks at the voice model's rate, or at
+    out_rate; the rolling context, the resamplers' FIFOs, the SOLA carry and the noise counters live on the device."""
 
-    def __init__(self, ctx, sid, cfg):
-        self._ctx, self.id, self.cfg = ctx, sid, cfg
+    def __init__(self, ctx, sid, cfg, io, upp):
+        self._ctx, self.id, self.cfg, self.io = ctx, sid, cfg, io
         self.n_streams = int(cfg.n_streams)
-        self.block_in = int(cfg.block_frames) * 160
-        self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))
+        self.in_channels = int(io.in_channels)
+        self.block_in = int(lib().rvcx_stream_in_len(ctx._h, sid))        # frames per block at the input rate
+        self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))      # samples per block as step() returns them
         self.noise_len = int(lib().rvcx_stream_noise_len(ctx._h, sid))
         self.frames = int(lib().rvcx_stream_frames(ctx._h, sid))          # T of the TextEncoder
-        upp = self.block_out // int(cfg.block_frames)
-        self.tail_len = (int(cfg.block_frames) + int(cfg.crossfade_frames) + int(cfg.search_frames)) * upp
-        self.skip_head = self.frames - self.tail_len // upp
+        din, dout = C.c_int32(0), C.c_int32(0)
+        ctx._ck(lib().rvcx_stream_delays(ctx._h, sid, C.byref(din), C.byref(dout)), "stream_delays")
+        self.in_delay, self.out_delay = int(din.value), int(dout.value)   # samples at 16 kHz / at the output rate
+        # model-rate lengths: upp comes from the library, not from block_out (the output may be resampled)
+        Fb = int(cfg.block_frames)
+        self.upp = int(upp)
+        self.block_native = Fb * self.upp
+        self.out_rate = 100 * self.block_out // Fb
+        self.out_resampled = self.out_rate != 100 * self.upp
+        self.tail_len = (Fb + int(cfg.crossfade_frames) + int(cfg.search_frames)) * self.upp
+        self.skip_head = self.frames - self.tail_len // self.upp
+        # the two resamplers' delays, plus the 10 ms of the p_len clamp (rvcx.h: the newest ring frame is not synthesized)
+        self.latency_ms = 1e3 * self.in_delay / 16000.0 + 1e3 * self.out_delay / float(self.out_rate) + 10.0
 
     def step(self, blocks, noise=None, taps=False):
-        """blocks (S, Fb * 160) float32 -> (S, Fb * upp) float32.  noise (S, noise_len): parity noise of this step (z_noise
-        then src_noise per stream).  taps=True: (out, pre_sola (S, tail_len), offsets (S,))."""
+        """blocks (S, block_in) float32 -- (S, block_in, in_channels) for in_channels > 1 -- -> (S, block_out) float32.
+        noise (S, noise_len): parity noise of this step (z_noise then src_noise per stream).  taps=True: (out, pre_sola
+        (S, tail_len), offsets (S,)), the latter two at the model's rate."""
         if self.id is None:
             raise RvcxError("StreamSession.step: the session is closed")
         S = self.n_streams
         x = f32(blocks)
-        if x.shape != (S, self.block_in):
-            raise RvcxError(f"StreamSession.step: blocks must be ({S}, {self.block_in}), got {x.shape}")
+        want = (S, self.block_in) if self.in_channels == 1 else (S, self.block_in, self.in_channels)
+        if x.shape != want:
+            raise RvcxError(f"StreamSession.step: blocks must be {want}, got {x.shape}")
         nz = None
         if noise is not None:
             nz = f32(noise)
@@ -385,12 +418,36 @@ class StreamSession:
         out = np.empty((S, self.block_out), np.float32)
         pre = np.empty((S, self.tail_len), np.float32) if taps else None
         offs = np.empty(S, np.int32) if taps else None
-
-        def table(a):
-            return None if a is None else (C.c_void_p * S)(*[a[i].ctypes.data for i in range(S)])
-        self._ctx._ck(lib().rvcx_stream_step(self._ctx._h, self.id, table(x), table(nz), table(out), table(pre),
-                                             _p(offs, C.c_int32)), "stream_step")
+        self._ctx._ck(lib().rvcx_stream_step(self._ctx._h, self.id, self._table(x), self._table(nz), self._table(out),
+                                             self._table(pre), _p(offs, C.c_int32)), "stream_step")
         return (out, pre, offs) if taps else out
+
+    def _table(self, a):
+        return None if a is None else (C.c_void_p * self.n_streams)(*[a[i].ctypes.data for i in range(self.n_streams)])
+
+    def last_taps(self):
+        """(in16k (S, Fb * 160), native (S, Fb * upp)) of the last successful step: the blocks that entered the rings and the
+        SOLA output in front of the output resampler (None when the output is not resampled: step() returned it)"""
+        S = self.n_streams
+        in16k = np.empty((S, int(self.cfg.block_frames) * 160), np.float32)
+        native = np.empty((S, self.block_native), np.float32) if self.out_resampled else None
+        self._ctx._ck(lib().rvcx_stream_last_taps(self._ctx._h, self.id, self._table(in16k), self._table(native)),
+                      "stream_last_taps")
+        return in16k, native
+
+    def set(self, pitches=None, sids=None, index_rate=None, protect=None):
+        """live controls, applied from the next step on (None keeps the current value); ring, FIFOs, carry and noise
+        counters are untouched.  A refused value (speaker id out of range, index of the wrong width) changes nothing."""
+        S = self.n_streams
+        pit = None if pitches is None else f32(np.atleast_1d(pitches))
+        sid = None if sids is None else i32(np.atleast_1d(sids))
+        if (pit is not None and pit.shape != (S,)) or (sid is not None and sid.shape != (S,)):
+            raise RvcxError("StreamSession.set: one pitch and one speaker id per stream")
+        nan = float("nan")
+        self._ctx._ck(lib().rvcx_stream_set(self._ctx._h, self.id, None if pit is None else pit.ctypes.data,
+                                            None if sid is None else sid.ctypes.data,
+                                            nan if index_rate is None else float(index_rate),
+                                            nan if protect is None else float(protect)), "stream_set")
 
     def reset(self):
         """zero ring, carry and step counter: the session then replays a fresh one"""
@@ -783,17 +840,34 @@ class Context:
         self._ck(lib().rvcx_op_sola(self._h, _p(y), _p(b), Lb, Lx, Ls, _p(out), _p(nb), C.byref(off), _p(sc)), "op_sola")
         return (out, nb, int(off.value), sc) if scores else (out, nb, int(off.value))
 
+    def stream_resample(self, x, sr_in: int, sr_out: int, block_frames: int) -> np.ndarray:
+        """rvcx_op_stream_resample: a session's resampler without a session.  x (S, frames) or (S, frames, channels) float32,
+        cut into blocks of block_frames * sr_in / 100 frames -> (S, frames * sr_out / sr_in) float32, delayed by
+        stream_resample_delay(sr_in, sr_out) samples."""
+        x = f32(x)
+        if x.ndim not in (2, 3):
+            raise RvcxError("stream_resample: x must be (S, frames) or (S, frames, channels)")
+        S, frames, ch = x.shape[0], x.shape[1], (1 if x.ndim == 2 else x.shape[2])
+        n_out = frames * int(sr_out) // max(int(sr_in), 1) if int(sr_in) > 0 and int(sr_out) > 0 else 0
+        y = np.empty((S, max(n_out, 0)), np.float32)
+        self._ck(lib().rvcx_op_stream_resample(self._h, x.ctypes.data, S, C.c_int64(frames), ch, int(sr_in), int(sr_out),
+                                               int(block_frames), y.ctypes.data), "op_stream_resample")
+        return y
+
     def stream_open(self, model_id, params: "Params", sids, pitches, block_frames, context_frames, crossfade_frames,
-                    search_frames) -> "StreamSession":
-        """rvcx_stream_open: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms)"""
+                    search_frames, in_rate=0, in_channels=1, out_rate=0) -> "StreamSession":
+        """rvcx_stream_open_io: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms).  in_rate /
+        in_channels: what step() takes (0 or 16000 with one channel: 16 kHz mono); out_rate: what it returns (0 or the
+        model's rate: the model's rate).  With the defaults this is rvcx_stream_open."""
         sid, pit = i32(np.atleast_1d(sids)), f32(np.atleast_1d(pitches))
         if sid.ndim != 1 or sid.shape != pit.shape or sid.shape[0] < 1:
             raise RvcxError("stream_open: one speaker id and one pitch per stream")
         cfg = StreamCfg(int(sid.shape[0]), int(block_frames), int(context_frames), int(crossfade_frames), int(search_frames))
+        io = StreamIO(int(in_rate), int(in_channels), int(out_rate), 0)
         h = C.c_int(0)
-        self._ck(lib().rvcx_stream_open(self._h, int(model_id), C.byref(cfg), C.byref(params), _p(sid, C.c_int32), _p(pit),
-                                        C.byref(h)), "stream_open")
-        return StreamSession(self, int(h.value), cfg)
+        self._ck(lib().rvcx_stream_open_io(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(params),
+                                           _p(sid, C.c_int32), _p(pit), C.byref(h)), "stream_open")
+        return StreamSession(self, int(h.value), cfg, io, self.synth_upp(model_id))
 
     def load_rmvpe(self, cfg_struct, state: dict):
         tbl, keep = make_table(state)

@@ -58,7 +58,17 @@ using TicketPtr = std::shared_ptr<Ticket>;
 // A live-stream session (rvcx_stream_open): S lock-step streams of one geometry on one voice model.  Ring, carry and block
 // staging are allocations of the session's own (the arena is scratch that other calls reset).  Ring and carry exist twice: a
 // step reads set `cur` and writes the other one, and the sets change places once the step has succeeded -- the body of a step
-// can then be repeated (range guard, BiGRU fallback) or fail without moving the session.
+// can then be repeated (range guard, BiGRU fallback) or fail without moving the session.  The same holds for the FIFOs of the
+// two resamplers of a session opened with rvcx_stream_open_io, for the dense blocks and for the native tap.
+//
+// One side of such a session (audio.hip, launch_stream_resample): plan, filter and the FIFO sets.  The tables are the
+// session's own device memory (built at open: make_resample_filter_at synchronises); two sides of one gain share them.
+struct StreamSide {
+  bool on = false;                         // false: that side is rvcx_stream_open's path
+  StreamResamplerPlan g;
+  ResampleFilter f;
+  double* fifo[2] = {nullptr, nullptr};    // (S, g.L) each; only when g.filter
+};
 struct StreamSession {
   int model_id = 0;
   std::weak_ptr<WeightRegion> region;      // expires when the voice model is unloaded (or replaced)
@@ -70,14 +80,21 @@ struct StreamSession {
   long Lb = 0, Lx = 0, Ls = 0, Lk = 0;     // block, cross-fade, search and synthesized tail in output samples
   float* ring[2] = {nullptr, nullptr};     // (S, N * 160) each
   float* carry[2] = {nullptr, nullptr};    // (S, Lx) each
-  float* blocks = nullptr;                 // (S, Fb * 160): the step's new blocks, dense
+  float* blocks[2] = {nullptr, nullptr};   // (S, Fb * 160) each: the step's new 16 kHz blocks, dense (set cur: the last step's)
+  rvcx_stream_io io{};
+  StreamSide in, out;                      // in: in_rate x in_channels -> 16 kHz mono; out: the model's rate -> out_rate
+  float* stage = nullptr;                  // in.on: (S, in.g.B_in * channels), the caller's blocks as they came
+  float* native[2] = {nullptr, nullptr};   // out.on: (S, Lb) each, SOLA output in front of the output resampler
+  double* tables[2] = {nullptr, nullptr};  // filter tables of the sides that filter (one allocation when they share a gain)
   int cur = 0;
   uint64_t step = 0;
   // RVCX_STREAM_FULL_SYNTH=1 (read at open; tools/bench_stream.py's A/B): the synthesizer runs with skip_head = 0 and SOLA takes
   // the tail of the whole output -- what the step costs without the tail-only path (and NOT what the reference computes)
   bool full_synth = false;
   ~StreamSession() {
-    for (float* q : {ring[0], ring[1], carry[0], carry[1], blocks})
+    for (void* q : {(void*)ring[0], (void*)ring[1], (void*)carry[0], (void*)carry[1], (void*)blocks[0], (void*)blocks[1],
+                    (void*)stage, (void*)native[0], (void*)native[1], (void*)tables[0], (void*)tables[1], (void*)in.fifo[0],
+                    (void*)in.fifo[1], (void*)out.fifo[0], (void*)out.fifo[1]})
       if (q) (void)hipFree(q);
   }
 };

@@ -19,6 +19,12 @@
 // One lane per output sample, left wing then right wing; ~2 x 290 taps per sample at 48 -> 16 kHz.
 // A 30 s stereo 48 kHz upload becomes 16 kHz mono in ~0.1 ms instead of ~1 s of host time -- at 1000x real time the
 // conversion itself takes 30 ms, so a host-side resampler would be the whole request.
+//
+// Live-stream sessions (rvcx.h, "live streams at the sound card's rate") run the same filter statefully, inside the step:
+// per stream a FIFO of past input in double, every output sample computed from its global index with the tap loop the
+// one-shot kernel uses (kaiser_exact_taps), so that what a session emits is the one-shot result on the whole signal, delayed
+// by stream_resample_delay() samples, however the signal was cut into blocks.
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <vector>
@@ -73,6 +79,37 @@ void build_window(const FilterSpec& F, double gain, std::vector<double>& win, st
   for (int i = 0; i < n; ++i) delta[i] = win[i + 1] - win[i];
 }
 
+// The tap loop of kaiser_hq for ONE output sample at input position `time_register`: tap i of the left wing sits at table
+// position (frac + i scale) table (floor + linear interpolation per tap), the left wing stops at input index 0, the right wing
+// in front of n_orig.  X(i) is input sample i as a double.  The one-shot kernel and the streaming kernel below both call this
+// one function: what a session emits is the one-shot filter, tap for tap.
+template <typename TAcc, typename XF>
+__device__ __forceinline__ TAcc kaiser_exact_taps(const ResampleFilter& f, double time_register, long n_orig, XF X) {
+  const double* __restrict__ win = f.win;
+  const double* __restrict__ delta = f.delta;
+  const long n = (long)time_register;
+  const double frac = f.scale * (time_register - (double)n);
+  TAcc acc = (TAcc)0;
+  const double step = f.scale * f.table;
+  double p0 = frac * f.table;
+  for (long i = 0; i <= n; ++i) {
+    const double p = p0 + (double)i * step;
+    const long idx = (long)p;
+    if (idx >= f.nwin - 1) break;
+    const double w = win[idx] + (p - (double)idx) * delta[idx];
+    acc = (TAcc)((double)acc + w * X(n - i));
+  }
+  p0 = (f.scale - frac) * f.table;
+  for (long k = 0; n + k + 1 < n_orig; ++k) {
+    const double p = p0 + (double)k * step;
+    const long idx = (long)p;
+    if (idx >= f.nwin - 1) break;
+    const double w = win[idx] + (p - (double)idx) * delta[idx];
+    acc = (TAcc)((double)acc + w * X(n + k + 1));
+  }
+  return acc;
+}
+
 template <typename TIn, typename TOut, typename TAcc>
 __global__ void resample_kernel(const TIn* __restrict__ x, long n_orig, long x_stride, int channels, TOut* __restrict__ y,
                                 long n_out, const ResampleFilter f) {
@@ -88,31 +125,13 @@ __global__ void resample_kernel(const TIn* __restrict__ x, long n_orig, long x_s
     return s / channels;
   };
   const double time_register = (double)t * f.time_increment;
+  if (f.exact) {
+    y[t] = (TOut)kaiser_exact_taps<TAcc>(f, time_register, n_orig, X);
+    return;
+  }
   const long n = (long)time_register;
   double frac = f.scale * (time_register - (double)n);
   TAcc acc = (TAcc)0;
-  if (f.exact) {
-    // tap i of the left wing sits at table position (frac + i scale) table: floor + linear interpolation per tap
-    const double step = f.scale * f.table;
-    double p0 = frac * f.table;
-    for (long i = 0; i <= n; ++i) {
-      const double p = p0 + (double)i * step;
-      const long idx = (long)p;
-      if (idx >= f.nwin - 1) break;
-      const double w = win[idx] + (p - (double)idx) * delta[idx];
-      acc = (TAcc)((double)acc + w * X(n - i));
-    }
-    p0 = (f.scale - frac) * f.table;
-    for (long k = 0; n + k + 1 < n_orig; ++k) {
-      const double p = p0 + (double)k * step;
-      const long idx = (long)p;
-      if (idx >= f.nwin - 1) break;
-      const double w = win[idx] + (p - (double)idx) * delta[idx];
-      acc = (TAcc)((double)acc + w * X(n + k + 1));
-    }
-    y[t] = (TOut)acc;
-    return;
-  }
   // resampy's published loop: a common fractional offset, an INTEGER table step
   const int index_step = f.index_step;
   double index_frac = frac * f.table;
@@ -135,6 +154,62 @@ __global__ void resample_kernel(const TIn* __restrict__ x, long n_orig, long x_s
   y[t] = (TOut)acc;
 }
 
+// ---- streaming (live-stream sessions, rvcx.h): per stream a FIFO of the last L = H + B_in mono samples in double
+// (the mean over channels is formed once, in double, exactly as X() above forms it; a float32 sample is a double exactly).
+// grid-stride over (S, L): dst row = src row moved left by B_in frames, the new block (S rows of B_in interleaved frames,
+// x_bs floats apart) mixed and appended.  src != dst: the two sets of a session.
+__global__ void stream_fifo_roll_kernel(const double* __restrict__ src, double* __restrict__ dst, const float* __restrict__ x,
+                                        long x_bs, int channels, long L, long B_in, long total) {
+  for (long idx = blockIdx.x * 256L + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long s = idx / L, j = idx - s * L;
+    double v;
+    if (j < L - B_in) {
+      v = src[idx + B_in];
+    } else {
+      const float* q = x + s * x_bs + (j - (L - B_in)) * channels;
+      if (channels == 1) {
+        v = (double)q[0];
+      } else {
+        double a = 0.0;
+        for (int c = 0; c < channels; ++c) a += (double)q[c];
+        v = a / channels;
+      }
+    }
+    dst[idx] = v;
+  }
+}
+
+// grid (ceil(B_out / 256), S): lane i of stream s emits global output sample t = t0 + i (0 where t < 0) from the FIFO row,
+// whose element 0 is global input sample `base` (negative while the session is young: those indices are never taps, the left
+// wing stops at 0) and whose end is the n_recv samples received so far (the right wing stops there).
+__global__ void stream_resample_kernel(const double* __restrict__ fifo, long L, long base, long n_recv, long t0,
+                                       float* __restrict__ y, long y_bs, long B_out, const ResampleFilter f) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= B_out) return;
+  const double* __restrict__ row = fifo + (long)blockIdx.y * L;
+  const long t = t0 + i;
+  float v = 0.f;
+  if (t >= 0) {
+    auto X = [&](long g) -> double {
+      const long j = g - base;
+      return (j >= 0 && j < L) ? row[j] : 0.0;      // (never outside: stream_resampler_plan's H; the test keeps a slip in bounds)
+    };
+    v = (float)kaiser_exact_taps<double>(f, (double)t * f.time_increment, n_recv, X);
+  }
+  y[(long)blockIdx.y * y_bs + i] = v;
+}
+
+// equal rates: no filter (librosa.resample returns its input), only the mono mix, rounded once to float32
+__global__ void stream_mix_kernel(const float* __restrict__ x, long x_bs, int channels, float* __restrict__ y, long y_bs,
+                                  long B) {
+  const long i = blockIdx.x * 256L + threadIdx.x;
+  if (i >= B) return;
+  const float* q = x + (long)blockIdx.y * x_bs + i * channels;
+  double a = 0.0;
+  for (int c = 0; c < channels; ++c) a += (double)q[c];
+  y[(long)blockIdx.y * y_bs + i] = (float)(channels == 1 ? a : a / channels);
+}
+
 }  // namespace
 
 long resample_out_len(long n, int sr_in, int sr_out) { return (long)((double)n * ((double)sr_out / (double)sr_in)); }
@@ -147,7 +222,12 @@ int resample_default_kind() {
   return k;
 }
 
-ResampleFilter make_resample_filter(Arena& A, int sr_in, int sr_out, hipStream_t s, int kind) {
+size_t resample_table_doubles(int kind) {
+  RVCX_CHECK(kind == 0 || kind == 1, "resample: unknown filter kind");
+  return 2 * ((size_t)kSpecs[kind].zeros * ((size_t)1 << kSpecs[kind].precision) + 1);
+}
+
+ResampleFilter make_resample_filter_at(double* d, int sr_in, int sr_out, hipStream_t s, int kind) {
   if (kind < 0) kind = resample_default_kind();
   RVCX_CHECK(kind == 0 || kind == 1, "resample: unknown filter kind");
   const FilterSpec& F = kSpecs[kind];
@@ -162,13 +242,17 @@ ResampleFilter make_resample_filter(Arena& A, int sr_in, int sr_out, hipStream_t
   RVCX_CHECK(f.index_step >= 1, "resample: ratio too small");
   std::vector<double> win, delta;
   build_window(F, ratio < 1.0 ? ratio : 1.0, win, delta);
-  double* d = A.alloc<double>(2 * (size_t)f.nwin);
   RVCX_HIP(hipMemcpyAsync(d, win.data(), (size_t)f.nwin * sizeof(double), hipMemcpyHostToDevice, s));
   RVCX_HIP(hipMemcpyAsync(d + f.nwin, delta.data(), (size_t)f.nwin * sizeof(double), hipMemcpyHostToDevice, s));
   RVCX_HIP(hipStreamSynchronize(s));          // the host vectors die with this frame
   f.win = d;
   f.delta = d + f.nwin;
   return f;
+}
+
+ResampleFilter make_resample_filter(Arena& A, int sr_in, int sr_out, hipStream_t s, int kind) {
+  if (kind < 0) kind = resample_default_kind();
+  return make_resample_filter_at(A.alloc<double>(resample_table_doubles(kind)), sr_in, sr_out, s, kind);
 }
 
 void launch_resample_f64(const ResampleFilter& f, const double* x, long n, int channels, double* y, long n_out,
@@ -183,6 +267,56 @@ void launch_resample_f32(const ResampleFilter& f, const float* x, long n, float*
   // float32 in -> float32 out with a float32 running sum: what the published loop does on a float32 array
   hipLaunchKernelGGL((resample_kernel<float, float, float>), dim3((unsigned)cdiv64(n_out, 256)), dim3(256), 0, s, x, n, 1L, 1,
                      y, n_out, f);
+}
+
+// ---- streaming: rules, geometry and the two launches of a step
+bool stream_rates_ok(int sr_in, int sr_out) {
+  auto one = [](int r, int other) { return r > 0 && r % 100 == 0 && r <= 192000 && (r >= 8000 || other < 8000); };
+  return one(sr_in, sr_out) && one(sr_out, sr_in);
+}
+
+int stream_resample_delay(int sr_in, int sr_out) {
+  if (!stream_rates_ok(sr_in, sr_out)) return -1;
+  if (sr_in == sr_out) return 0;
+  return sr_out > sr_in ? (int)((96L * sr_out + sr_in - 1) / sr_in) : 96;      // ceil(96 max(1, sr_out / sr_in))
+}
+
+StreamResamplerPlan stream_resampler_plan(int sr_in, int sr_out, int channels, int block_frames) {
+  RVCX_CHECK(stream_rates_ok(sr_in, sr_out) && channels >= 1 && block_frames >= 1, "stream resampler: bad geometry");
+  StreamResamplerPlan g;
+  g.sr_in = sr_in, g.sr_out = sr_out, g.channels = channels;
+  g.B_in = (long)block_frames * (sr_in / 100);
+  g.B_out = (long)block_frames * (sr_out / 100);
+  g.delay = stream_resample_delay(sr_in, sr_out);
+  g.filter = sr_in != sr_out;
+  if (!g.filter) return g;
+  // History.  Step k (R = (k + 1) B_in frames received) emits t in [k B_out - d, (k + 1) B_out - d).  For t >= 0 the tap loop
+  // reads input n - i (left) and n + k' + 1 (right) with n = floor(t inc), inc = sr_in / sr_out, while (frac + i scale) < 96:
+  // at most W = ceil(96 / scale) taps per wing, one more if the last bit of p rounds down (its weight is the table's zero end).
+  // The computed n is the real floor, or one less where t inc is an integer that rounds below itself; so for the first sample
+  // of a step n >= (k B_out - d) inc - 1 = k B_in - d inc - 1 and the lowest index read is >= k B_in - ceil(d inc) - 1 - W.
+  // The FIFO's first element is global sample R - L = k B_in - H, so H = ceil(d inc) + W + 2 leaves one sample to spare.
+  // No tap lies at or beyond R: the right wing stops in front of n_recv = R (and the delay makes that bound idle).
+  const long d_in = ((long)g.delay * sr_in + sr_out - 1) / sr_out;
+  const long W = sr_out < sr_in ? (96L * sr_in + sr_out - 1) / sr_out : 96;
+  g.H = d_in + W + 2;
+  g.L = g.H + g.B_in;
+  return g;
+}
+
+void launch_stream_resample(const StreamResamplerPlan& g, const ResampleFilter& f, const double* fifo_cur, double* fifo_next,
+                            const float* x, long x_bs, float* y, long y_bs, int S, uint64_t step, hipStream_t s) {
+  if (!g.filter) {
+    hipLaunchKernelGGL(stream_mix_kernel, dim3((unsigned)cdiv64(g.B_out, 256), S), dim3(256), 0, s, x, x_bs, g.channels, y, y_bs,
+                       g.B_out);
+    return;
+  }
+  const long tot = (long)S * g.L;
+  hipLaunchKernelGGL(stream_fifo_roll_kernel, dim3((unsigned)std::min<long>(cdiv64(tot, 256), 1 << 16)), dim3(256), 0, s,
+                     fifo_cur, fifo_next, x, x_bs, g.channels, g.L, g.B_in, tot);
+  const long n_recv = ((long)step + 1) * g.B_in;
+  hipLaunchKernelGGL(stream_resample_kernel, dim3((unsigned)cdiv64(g.B_out, 256), S), dim3(256), 0, s, fifo_next, g.L,
+                     n_recv - g.L, n_recv, (long)step * g.B_out - g.delay, y, y_bs, g.B_out, f);
 }
 
 }  // namespace rvcx

@@ -142,6 +142,27 @@ ResampleFilter make_resample_filter(Arena& A, int sr_in, int sr_out, hipStream_t
 void launch_resample_f64(const ResampleFilter& f, const double* x, long n, int channels, double* y, long n_out,
                          hipStream_t s);
 void launch_resample_f32(const ResampleFilter& f, const float* x, long n, float* y, long n_out, hipStream_t s);
+// the same filter with its two tables (resample_table_doubles(kind) doubles) in memory the caller owns; synchronises `s`
+size_t resample_table_doubles(int kind);
+ResampleFilter make_resample_filter_at(double* tables, int sr_in, int sr_out, hipStream_t s, int kind);
+
+// ---- audio.hip: the stateful resampler of live-stream sessions (rvcx.h "live streams": filter, delay, global index).
+// Always kaiser_hq.  Rates: multiples of 100 Hz within 8000 .. 192000 (a rate below 8000 only beside a partner below 8000:
+// reduced-size voice models); -1 / false otherwise.
+bool stream_rates_ok(int sr_in, int sr_out);
+int stream_resample_delay(int sr_in, int sr_out);      // output samples: 0 for equal rates, else ceil(96 max(1, sr_out / sr_in))
+struct StreamResamplerPlan {
+  int sr_in = 0, sr_out = 0, channels = 1, delay = 0;
+  bool filter = false;            // false: equal rates, a step is the mono mix alone (no FIFO, no tables)
+  long B_in = 0, B_out = 0;       // frames per block in and samples per block out
+  long H = 0, L = 0;              // history frames in front of the newest block, and the FIFO row L = H + B_in (doubles)
+};
+StreamResamplerPlan stream_resampler_plan(int sr_in, int sr_out, int channels, int block_frames);
+// one step of S streams: FIFO rows (S, L) of set `fifo_cur` roll into `fifo_next` with the new blocks x (S rows of B_in
+// interleaved frames, x_bs floats apart) mixed to mono in double, then y (S rows of B_out, y_bs apart) is computed from
+// fifo_next.  `step` = blocks taken since open / reset.  Two launches, no state but the FIFO: repeating a step repeats its bits.
+void launch_stream_resample(const StreamResamplerPlan& g, const ResampleFilter& f, const double* fifo_cur, double* fifo_next,
+                            const float* x, long x_bs, float* y, long y_bs, int S, uint64_t step, hipStream_t s);
 
 // ---- stream.hip: live-stream sessions
 // rows (S, n) of 16 kHz samples: dst row = src row shifted left by `blk` samples with block s appended (src != dst).

@@ -5,10 +5,16 @@ block 100 ms, context 2.5 s, cross-fade 50 ms, search 10 ms; S lock-step streams
 p99 per run, and the per-stage device times of rvcx_last_timing.  Then the same step with the synthesizer run whole
 (RVCX_STREAM_FULL_SYNTH=1: skip_head = 0, SOLA on the tail of the output): what the tail-only path saves.
 
+With `--in-rate` / `--in-channels` / `--out-rate` every S is measured a second time as a rate session (rvcx_stream_open_io:
+the blocks arrive at the sound card's rate and leave at `--out-rate`), on the same model and the same audio, so the step with
+and without the two resamplers stands side by side; the result gains the delays and the difference.  `--model 40k` measures
+on the 40 k voice model (48 kHz out of it is a real conversion; out of the 48 k model it is none).
+
 The one criterion that can be derived is real time itself: a step must take less than the block it converts.  The result
 records, per S, whether the median and the p99 do, and the largest S whose p99 does.  Not part of bench.py.
 
-    python tools/bench_stream.py [--streams 1,4,16,32] [--steps 200] [--warmup 20] [--repeats 3] [--out profiles/bench_stream.json]"""
+    python tools/bench_stream.py [--streams 1,4,16,32] [--steps 200] [--warmup 20] [--repeats 3] [--model 48k|40k]
+                                 [--in-rate 48000 --in-channels 2 --out-rate 48000] [--out profiles/bench_stream.json]"""
 import argparse
 import json
 import os
@@ -28,20 +34,34 @@ BLOCK_MS, CONTEXT_MS, CROSSFADE_MS, SEARCH_MS = 100, 2500, 50, 10
 STAGES = ["f0", "hubert", "blend_mix", "enc_p", "flow", "decoder", "sola_copies", "total"]
 
 
-def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth):
+def mic_blocks(clips, in_rate, in_channels):
+    """the 16 kHz clips as a sound card would deliver them: (S, frames at in_rate[, channels]); sample-and-hold is enough for a
+    timing run (the step does not depend on the values)"""
+    if in_rate in (0, 16000) and in_channels == 1:
+        return clips
+    rate = in_rate or 16000
+    idx = (np.arange(clips.shape[1] * rate // 16000) * 16000) // rate
+    x = clips[:, idx]
+    return x if in_channels == 1 else np.ascontiguousarray(np.repeat(x[:, :, None], in_channels, axis=2))
+
+
+def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None):
     os.environ["RVCX_STREAM_FULL_SYNTH"] = "1" if full_synth else "0"      # read when the session opens
     p = bench.make_params(seed=1)
+    io = io or {}
     Fb, Fc, Fx, Fs = BLOCK_MS // 10, CONTEXT_MS // 10, CROSSFADE_MS // 10, SEARCH_MS // 10
     need = (warmup + steps) * Fb * 160
     clips = np.stack([S.make_clip(100 + s, need / 16000.0 + 0.1)[:need] for s in range(n_streams)]).astype(np.float32)
+    clips = mic_blocks(clips, io.get("in_rate", 0), io.get("in_channels", 1))
     runs, stage_ms = [], []
-    with ctx.stream_open(mid, p, [0] * n_streams, [float(s % 5 - 2) for s in range(n_streams)], Fb, Fc, Fx, Fs) as se:
-        geo = dict(ring_frames=Fc + Fx + Fs + Fb, frames=se.frames, skip_head=se.skip_head, block_out=se.block_out)
+    with ctx.stream_open(mid, p, [0] * n_streams, [float(s % 5 - 2) for s in range(n_streams)], Fb, Fc, Fx, Fs, **io) as se:
+        geo = dict(ring_frames=Fc + Fx + Fs + Fb, frames=se.frames, skip_head=se.skip_head, block_in=se.block_in,
+                   block_out=se.block_out, in_delay=se.in_delay, out_delay=se.out_delay, latency_ms=round(se.latency_ms, 3))
         for r in range(repeats):
             se.reset()
             ms = []
             for k in range(warmup + steps):
-                blk = np.ascontiguousarray(clips[:, k * Fb * 160:(k + 1) * Fb * 160])
+                blk = np.ascontiguousarray(clips[:, k * se.block_in:(k + 1) * se.block_in])
                 t0 = time.perf_counter()
                 out = se.step(blk)
                 dt = time.perf_counter() - t0
@@ -53,7 +73,7 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth):
             ms = np.asarray(ms)
             runs.append(dict(median_ms=round(float(np.median(ms)), 3), p99_ms=round(float(np.percentile(ms, 99)), 3),
                              max_ms=round(float(ms.max()), 3)))
-            print(f"  S={n_streams} full_synth={int(full_synth)} run {r}: {runs[-1]}", flush=True)
+            print(f"  S={n_streams} full_synth={int(full_synth)} io={io} run {r}: {runs[-1]}", flush=True)
     st = np.median(np.asarray(stage_ms), axis=0)
     return dict(geometry=geo, runs=runs, median_ms=round(float(np.median([r["median_ms"] for r in runs])), 3),
                 p99_ms=round(float(np.max([r["p99_ms"] for r in runs])), 3),
@@ -67,22 +87,37 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--ab-steps", type=int, default=60, help="timed steps of the skip_head = 0 comparison (one run)")
+    ap.add_argument("--model", default="48k", choices=["48k", "40k"], help="the voice model the sessions run on")
+    ap.add_argument("--in-rate", type=int, default=0, help="Hz of the blocks a rate session takes (0: 16 kHz)")
+    ap.add_argument("--in-channels", type=int, default=1)
+    ap.add_argument("--out-rate", type=int, default=0, help="Hz of the blocks a rate session returns (0: the model's rate)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_stream.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_stream: no GPU visible (there is no CPU path)")
     ctx = _lib.Context(0)
-    mid = bench.load_models(ctx)
+    mid = bench.load_models(ctx, also_40k=True)[1] if a.model == "40k" else bench.load_models(ctx)
     name, _ = _lib.device_info(0)
-    res = dict(metric="stream_step_ms", device=name, block_ms=BLOCK_MS, context_ms=CONTEXT_MS, crossfade_ms=CROSSFADE_MS,
-               search_ms=SEARCH_MS, steps=a.steps, warmup=a.warmup, repeats=a.repeats, streams={})
+    io = dict(in_rate=a.in_rate, in_channels=a.in_channels, out_rate=a.out_rate)
+    rates = io != dict(in_rate=0, in_channels=1, out_rate=0)
+    res = dict(metric="stream_step_ms", device=name, model=a.model, block_ms=BLOCK_MS, context_ms=CONTEXT_MS,
+               crossfade_ms=CROSSFADE_MS, search_ms=SEARCH_MS, steps=a.steps, warmup=a.warmup, repeats=a.repeats, streams={})
+    if rates:
+        res["io"] = io
     for n_streams in [int(v) for v in a.streams.split(",")]:
         r = run(ctx, mid, n_streams, a.steps, a.warmup, a.repeats, False)
-        full = run(ctx, mid, n_streams, a.ab_steps, a.warmup, 1, True)
+        if a.ab_steps > 0:
+            full = run(ctx, mid, n_streams, a.ab_steps, a.warmup, 1, True)
+            r["skip_head_0"] = dict(median_ms=full["median_ms"], p99_ms=full["p99_ms"], stage_ms_median=full["stage_ms_median"])
+            r["tail_only_saves_ms"] = round(full["median_ms"] - r["median_ms"], 3)
         r["real_time_median"] = bool(r["median_ms"] < BLOCK_MS)
         r["real_time_p99"] = bool(r["p99_ms"] < BLOCK_MS)
-        r["skip_head_0"] = dict(median_ms=full["median_ms"], p99_ms=full["p99_ms"], stage_ms_median=full["stage_ms_median"])
-        r["tail_only_saves_ms"] = round(full["median_ms"] - r["median_ms"], 3)
+        if rates:     # the same S, model and audio through the two resamplers: the step with and without, side by side
+            q = run(ctx, mid, n_streams, a.steps, a.warmup, a.repeats, False, io)
+            r["rates"] = dict(geometry=q["geometry"], runs=q["runs"], median_ms=q["median_ms"], p99_ms=q["p99_ms"],
+                              stage_ms_median=q["stage_ms_median"], real_time_p99=bool(q["p99_ms"] < BLOCK_MS),
+                              resampling_costs_ms=round(q["median_ms"] - r["median_ms"], 3),
+                              resampling_costs_device_ms=round(q["stage_ms_median"]["total"] - r["stage_ms_median"]["total"], 3))
         res["streams"][str(n_streams)] = r
     ok = [int(k) for k, v in res["streams"].items() if v["real_time_p99"]]
     res["largest_streams_real_time_p99"] = max(ok) if ok else 0
