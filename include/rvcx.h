@@ -483,11 +483,117 @@ int rvcx_stream_set(rvcx_ctx*, int stream_id, const float* pitch, const int32_t*
 int rvcx_op_stream_resample(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int channels, int sr_in, int sr_out,
                             int block_frames, float* y_hd);
 
+/* ---- post-production -------------------------------------------------------------------------------------------------
+ * The reference's second workflow (rvc/scripts/audio_processing.py: convert_to_stereo -> add_effects -> combine_audio) on the
+ * device.  add_effects is a pedalboard board and combine_audio is pydub; neither package nor its source is part of the
+ * reference tree, so the stages are DEFINED here.  Parity with pedalboard's JUCE classes is unpinned (as for torchcrepe);
+ * what is pinned is this arithmetic, against float64 and scipy.signal.lfilter.
+ *
+ * Signal: float32, B items of C in {1, 2} channels and n[b] frames each, interleaved (frames, channels) at the ABI, planar on
+ * the device.  sr: any multiple of 100 Hz in 8000 .. 192000.  Coefficients are formed on the host in double and rounded once to
+ * float32.  All state is zero at sample 0.  No parameter smoothing.  Stage order = the board's (audio_processing.py:76-102).  A
+ * stage whose parameters make it the identity ("skip") is not launched: its output is its input bit for bit.
+ *
+ *  1 high-pass, first order, fc = 50 Hz: k = tan(pi fc / sr), b0 = 1 / (k + 1), b1 = -b0, a1 = (k - 1) / (k + 1);
+ *    y[n] = b0 x[n] + b1 x[n-1] - a1 y[n-1].
+ *  2 compressor (ratio, threshold_db; attack 1 ms, release 100 ms), per channel.  cte(ms) = ms < 1e-3 ? 0 :
+ *    exp(-2 pi 1000 / (ms sr)).  Envelope e[n] = |x[n]| + c (e[n-1] - |x[n]|), c = cte(attack) when |x[n]| > e[n-1], else
+ *    cte(release).  thr = 10^(dB / 20); g = e < thr ? 1 : pow(e / thr, 1 / ratio - 1); y = x g.  Skip when ratio == 1.
+ *  3 noise gate (threshold_db, ratio, attack_ms, release_ms), per channel: two followers in series.  r[n] follows x^2 with
+ *    attack 0 ms and release 50 ms and outputs sqrt(r[n]); e[n] is the follower of stage 2 on that output with the caller's
+ *    attack and release.  g = e > thr ? 1 : pow(e / thr, ratio - 1).  Skip when ratio == 1.
+ *  4 reverb: Freeverb (room_size, damping, wet, dry, width), stereo only, never skipped.  in = 0.015 (L + R);
+ *    fb = 0.28 room_size + 0.7; d = 0.4 damping.  Eight parallel combs per side, delays {1116, 1188, 1277, 1356, 1422, 1491,
+ *    1557, 1617}, then four all-passes in series, delays {556, 441, 341, 225}; the right side adds 23 to every delay; a delay
+ *    of D becomes (int64) sr D / 44100 samples.  Comb: o = buf[i]; last = o (1 - d) + last d; buf[i] = in + last fb; the comb
+ *    outputs o are summed in the listed order.  All-pass: v = buf[i]; buf[i] = in + 0.5 v; out = v - in.
+ *    w1 = 1.5 wet (1 + width), w2 = 1.5 wet (1 - width); L' = oL w1 + oR w2 + 2 dry L, mirrored for R' (2 dry is ONE
+ *    float32 coefficient).
+ *  5 low shelf, 6 high shelf (gain_db; fc = 440 Hz, Q = 1 / sqrt 2): the audio-EQ-cookbook shelving biquads with
+ *    A = 10^(dB / 40), w = 2 pi fc / sr, beta = sin w sqrt(A) / Q, normalised by a0, transposed direct form II
+ *    (y = b0 x + s1; s1 = b1 x - a1 y + s2; s2 = b2 x - a2 y).  Skip at 0 dB.
+ *  7 chorus (rate_hz, depth, centre_delay_ms, feedback, mix), per channel -- the project's own definition:
+ *    tau(n) = sr / 1000 max(1, centre_ms + 10 depth sin(2 pi rate n / sr)) samples (evaluated in double);
+ *    w[n] = the line d at n - tau(n), linear interpolation d[i] + frac (d[i+1] - d[i]), zero in front of sample 0;
+ *    d[n] = x[n] + feedback w[n]; y = (1 - mix) x + mix w.  |feedback| < 1.  Skip at mix == 0 (the UI's default).
+ *  8 mix (combine_audio, :29-40), pydub's int16 arithmetic: both inputs stereo int16 at the vocal's rate; every sample s
+ *    becomes clip(floor(s 10^(gain_db / 20))) (the product in double), then a saturating add.  The result has the vocal's
+ *    length: a longer instrumental is cut, a shorter one padded with zeros.
+ *
+ * How the recurrences run wide (csrc/effects.hip): linear stages as a chunked scan of affine 2 x 2 maps;
+ * followers by relaxation over chunks of rvcx_fx_chunk() samples -- every chunk from a guessed state, re-run while its
+ * initial state differs from its predecessor's final state, at most as many passes as the longest row has chunks -- which
+ * ends in the sequential result bit for bit (every rounding of a step is explicit and the same on host and device); combs,
+ * all-passes and the chorus in blocks of their shortest delay.
+ *
+ * Errors: a rate or channel count out of range, ratio < 1, |feedback| >= 1, a value that is not finite, and reverb on mono
+ * return -1 with a message and write nothing.  Entry points with a context hold its mutex and complete the tickets in flight first.
+ * Scratch is the activation arena: when B items do not fit its budget (or exceed RVCX_MAX_BATCH, when set), rvcx_fx_chain
+ * runs them in groups; an item's result does not depend on the grouping, bit for bit. */
+typedef struct {
+  /* the eighteen values of add_effects (audio_processing.py:54-75), in its order */
+  float reverb_rm_size, reverb_wet, reverb_dry, reverb_damping, reverb_width;
+  float low_shelf_gain, high_shelf_gain;
+  float compressor_ratio, compressor_threshold;
+  float noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release;
+  float chorus_rate_hz, chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix;
+  int32_t sample_rate, channels;
+} rvcx_fx_params;
+/* the whole board on B items: x_hd[b] / y_hd[b] hold n[b] x channels floats (channels must be 2: the reverb is in it).
+ * rvcx_last_timing afterwards: {high-pass, compressor, gate, reverb, low shelf, high shelf, chorus, copies + layout, total} */
+int rvcx_fx_chain(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, const rvcx_fx_params*, float* const* y_hd);
+/* one stage on one item, x and y (n, channels) interleaved; the chain's fixed values are arguments here.  env_hd (optional,
+ * (n, channels)): the envelope e[n] the gain was computed from. */
+int rvcx_op_fx_highpass(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float fc, float* y_hd);
+int rvcx_op_fx_compressor(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float ratio, float threshold_db,
+                          float attack_ms, float release_ms, float* y_hd, float* env_hd);
+int rvcx_op_fx_gate(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float threshold_db, float ratio,
+                    float attack_ms, float release_ms, float* y_hd, float* env_hd);
+int rvcx_op_fx_reverb(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float room_size, float damping, float wet,
+                      float dry, float width, float* y_hd);
+int rvcx_op_fx_shelf(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, int high, float gain_db, float fc, float Q,
+                     float* y_hd);
+int rvcx_op_fx_chorus(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float rate_hz, float depth,
+                      float centre_delay_ms, float feedback, float mix, float* y_hd);
+/* stage 8: vocal (n_v, 2) and instrumental (n_i, 2) int16 -> out (n_v, 2) int16 */
+int rvcx_op_fx_mix(rvcx_ctx*, const int16_t* vocal_hd, int64_t n_v, const int16_t* inst_hd, int64_t n_i, float vocal_gain_db,
+                   float inst_gain_db, int16_t* out_hd);
+/* samples per chunk of the scan and follower kernels */
+int rvcx_fx_chunk(void);
+/* relaxation passes of the last rvcx_fx_chain / compressor / gate call that ran at least one chunk: {compressor, gate's
+ * x^2 follower, gate's peak follower} (0: stage not run; the largest over the groups of a chain); returns the number of
+ * groups that call ran in, -1 without a context */
+int rvcx_fx_last_passes(rvcx_ctx*, int32_t* passes3);
+/* Host only, no context, no GPU: the pieces of the definitions above and each stage run sequentially in float32 in the
+ * defined order (one channel).  -1 (message via rvcx_last_error(NULL)) and nothing written for arguments out of range. */
+float rvcx_fx_cte(double ms, int sr);
+int rvcx_fx_delay(int sr, int D);
+/* kind 0: stage 1 (Q, gain_db unused; coef5[2] = coef5[4] = 0), 1: low shelf, 2: high shelf -> {b0, b1, b2, a1, a2} */
+int rvcx_fx_coeffs(int kind, int sr, double fc, double Q, double gain_db, float* coef5);
+int rvcx_fx_highpass_host(const float* x, int64_t n, int sr, float fc, float* y);
+int rvcx_fx_biquad_host(const float* x, int64_t n, const float* coef5, float* y);
+/* env[n] = follower of |x| (square = 0) or x^2 (square = 1) with the constants c_attack / c_release (rvcx_fx_cte values);
+ * sqrt_out != 0 writes sqrt(e[n]) */
+int rvcx_fx_follower_host(const float* x, int64_t n, int square, int sqrt_out, float c_attack, float c_release, float* env);
+/* stages 2 and 3 whole on one channel (followers + gain); env optional */
+int rvcx_fx_compressor_host(const float* x, int64_t n, int sr, float ratio, float threshold_db, float attack_ms,
+                            float release_ms, float* y, float* env);
+int rvcx_fx_gate_host(const float* x, int64_t n, int sr, float threshold_db, float ratio, float attack_ms, float release_ms,
+                      float* y, float* env);
+/* one comb (delay D samples, feedback fb, damping d = 0.4 damping) / one all-pass on a given input */
+int rvcx_fx_comb_host(const float* in, int64_t n, int D, float fb, float d, float* out);
+int rvcx_fx_allpass_host(const float* in, int64_t n, int D, float* out);
+int rvcx_fx_chorus_host(const float* x, int64_t n, int sr, float rate_hz, float depth, float centre_delay_ms, float feedback,
+                        float mix, float* y);
+int rvcx_fx_mix_host(const int16_t* vocal, int64_t n_v, const int16_t* inst, int64_t n_i, float vocal_gain_db,
+                     float inst_gain_db, int16_t* out);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
  * {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} -- a session's input resampler is counted in the
- * F0 interval, its output resampler in "SOLA + copies" */
+ * F0 interval, its output resampler in "SOLA + copies"; of the last rvcx_fx_chain: {high-pass, compressor, gate, reverb, low
+ * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups) */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration

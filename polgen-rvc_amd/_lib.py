@@ -71,6 +71,37 @@ class UttExtra(C.Structure):
 F0_RMVPE, F0_FCPE, F0_CREPE = 0, 1, 2        # rvcx_params.f0_method
 
 
+FX_FIELDS = ("reverb_rm_size", "reverb_wet", "reverb_dry", "reverb_damping", "reverb_width", "low_shelf_gain",
+             "high_shelf_gain", "compressor_ratio", "compressor_threshold", "noise_gate_threshold", "noise_gate_ratio",
+             "noise_gate_attack", "noise_gate_release", "chorus_rate_hz", "chorus_depth", "chorus_centre_delay_ms",
+             "chorus_feedback", "chorus_mix")
+
+
+class FxParams(C.Structure):
+    """rvcx_fx_params: the eighteen values of add_effects (audio_processing.py:54-75) in its order, then rate and channels"""
+    _fields_ = [(k, C.c_float) for k in FX_FIELDS] + [("sample_rate", C.c_int32), ("channels", C.c_int32)]
+
+    @classmethod
+    def make(cls, values, sample_rate, channels=2):
+        """values: the eighteen add_effects values in order, or a dict of them"""
+        p = cls()
+        if isinstance(values, dict):
+            values = [values[k] for k in FX_FIELDS]
+        if len(values) != len(FX_FIELDS):
+            raise RvcxError(f"FxParams: {len(FX_FIELDS)} effect values expected, got {len(values)}")
+        for k, v in zip(FX_FIELDS, values):
+            setattr(p, k, float(v))
+        p.sample_rate, p.channels = int(sample_rate), int(channels)
+        return p
+
+
+# the processing tab's defaults (tabs/processing/processing.py): chorus off, shelves flat
+FX_UI_DEFAULTS = dict(reverb_rm_size=0.1, reverb_wet=0.1, reverb_dry=0.8, reverb_damping=0.9, reverb_width=1.0,
+                      low_shelf_gain=0, high_shelf_gain=0, compressor_ratio=4, compressor_threshold=-12,
+                      noise_gate_threshold=-40, noise_gate_ratio=8, noise_gate_attack=10, noise_gate_release=100,
+                      chorus_rate_hz=0, chorus_depth=0, chorus_centre_delay_ms=0, chorus_feedback=0, chorus_mix=0)
+
+
 class StreamIO(C.Structure):
     """rvcx_stream_io: the rates at the two edges of a live-stream session (0: none on that side)"""
     _fields_ = [("in_rate", C.c_int32), ("in_channels", C.c_int32), ("out_rate", C.c_int32), ("reserved", C.c_int32)]
@@ -133,6 +164,10 @@ SYMBOLS = [
     "rvcx_stream_out_len", "rvcx_stream_noise_len", "rvcx_stream_frames",
     "rvcx_stream_open_io", "rvcx_stream_in_len", "rvcx_stream_delays", "rvcx_stream_resample_delay", "rvcx_stream_last_taps",
     "rvcx_stream_set", "rvcx_op_stream_resample",
+    "rvcx_fx_chain", "rvcx_op_fx_highpass", "rvcx_op_fx_compressor", "rvcx_op_fx_gate", "rvcx_op_fx_reverb", "rvcx_op_fx_shelf",
+    "rvcx_op_fx_chorus", "rvcx_op_fx_mix", "rvcx_fx_chunk", "rvcx_fx_last_passes", "rvcx_fx_cte", "rvcx_fx_delay",
+    "rvcx_fx_coeffs", "rvcx_fx_highpass_host", "rvcx_fx_biquad_host", "rvcx_fx_follower_host", "rvcx_fx_compressor_host",
+    "rvcx_fx_gate_host", "rvcx_fx_comb_host", "rvcx_fx_allpass_host", "rvcx_fx_chorus_host", "rvcx_fx_mix_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
@@ -203,7 +238,137 @@ def lib() -> C.CDLL:
         _lib.rvcx_op_gru_input.argtypes = [vp, fp, C.c_int, C.c_int, C.c_int, C.c_int, fp]
         _lib.rvcx_op_upsample_protect.argtypes = [vp, fp, fp, fp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int,
                                                   C.c_int, fp]
+        f, d, i, i64 = C.c_float, C.c_double, C.c_int, C.c_int64
+        _lib.rvcx_fx_chain.argtypes = [vp, i, vp, vp, C.POINTER(FxParams), vp]
+        _lib.rvcx_op_fx_highpass.argtypes = [vp, vp, i64, i, i, f, vp]
+        _lib.rvcx_op_fx_compressor.argtypes = [vp, vp, i64, i, i, f, f, f, f, vp, vp]
+        _lib.rvcx_op_fx_gate.argtypes = [vp, vp, i64, i, i, f, f, f, f, vp, vp]
+        _lib.rvcx_op_fx_reverb.argtypes = [vp, vp, i64, i, i, f, f, f, f, f, vp]
+        _lib.rvcx_op_fx_shelf.argtypes = [vp, vp, i64, i, i, i, f, f, f, vp]
+        _lib.rvcx_op_fx_chorus.argtypes = [vp, vp, i64, i, i, f, f, f, f, f, vp]
+        _lib.rvcx_op_fx_mix.argtypes = [vp, vp, i64, vp, i64, f, f, vp]
+        _lib.rvcx_fx_last_passes.argtypes = [vp, vp]
+        _lib.rvcx_fx_cte.argtypes, _lib.rvcx_fx_cte.restype = [d, i], f
+        _lib.rvcx_fx_delay.argtypes = [i, i]
+        _lib.rvcx_fx_coeffs.argtypes = [i, i, d, d, d, vp]
+        _lib.rvcx_fx_highpass_host.argtypes = [vp, i64, i, f, vp]
+        _lib.rvcx_fx_biquad_host.argtypes = [vp, i64, vp, vp]
+        _lib.rvcx_fx_follower_host.argtypes = [vp, i64, i, i, f, f, vp]
+        _lib.rvcx_fx_compressor_host.argtypes = [vp, i64, i, f, f, f, f, vp, vp]
+        _lib.rvcx_fx_gate_host.argtypes = [vp, i64, i, f, f, f, f, vp, vp]
+        _lib.rvcx_fx_comb_host.argtypes = [vp, i64, i, f, f, vp]
+        _lib.rvcx_fx_allpass_host.argtypes = [vp, i64, i, vp]
+        _lib.rvcx_fx_chorus_host.argtypes = [vp, i64, i, f, f, f, f, f, vp]
+        _lib.rvcx_fx_mix_host.argtypes = [vp, i64, vp, i64, f, f, vp]
     return _lib
+
+
+# ---- post-production on the host (rvcx.h "post-production": no GPU, no context; one channel, float32, sequential) ----------
+def _fx_host(name, rc):
+    if rc != 0:
+        raise RvcxError(f"{name}: " + (lib().rvcx_last_error(None) or b"").decode())
+
+
+def fx_chunk() -> int:
+    """samples per chunk of the scan and follower kernels"""
+    return int(lib().rvcx_fx_chunk())
+
+
+def fx_cte(ms: float, sr: int) -> np.float32:
+    return np.float32(lib().rvcx_fx_cte(float(ms), int(sr)))
+
+
+def fx_delay(sr: int, D: int) -> int:
+    return int(lib().rvcx_fx_delay(int(sr), int(D)))
+
+
+def fx_coeffs(kind: int, sr: int, fc: float, Q: float = 2.0 ** -0.5, gain_db: float = 0.0) -> np.ndarray:
+    """float32 {b0, b1, b2, a1, a2}: kind 0 the first-order high-pass, 1 the low shelf, 2 the high shelf"""
+    c = np.zeros(5, np.float32)
+    _fx_host("fx_coeffs", lib().rvcx_fx_coeffs(int(kind), int(sr), float(fc), float(Q), float(gain_db), c.ctypes.data))
+    return c
+
+
+def _fx_out(x, y):
+    return np.empty_like(x) if y is None else y
+
+
+def fx_highpass_host(x, sr, fc=50.0, out=None):
+    x = f32(x)
+    y = _fx_out(x, out)
+    _fx_host("fx_highpass_host", lib().rvcx_fx_highpass_host(x.ctypes.data, x.shape[0], int(sr), float(fc), y.ctypes.data))
+    return y
+
+
+def fx_biquad_host(x, coef5):
+    x, c = f32(x), f32(coef5)
+    y = np.empty_like(x)
+    _fx_host("fx_biquad_host", lib().rvcx_fx_biquad_host(x.ctypes.data, x.shape[0], c.ctypes.data, y.ctypes.data))
+    return y
+
+
+def fx_follower_host(x, c_attack, c_release, square=False, sqrt_out=False, out=None):
+    x = f32(x)
+    y = _fx_out(x, out)
+    _fx_host("fx_follower_host", lib().rvcx_fx_follower_host(x.ctypes.data, x.shape[0], int(square), int(sqrt_out),
+                                                             float(c_attack), float(c_release), y.ctypes.data))
+    return y
+
+
+def fx_compressor_host(x, sr, ratio, threshold_db, attack_ms=1.0, release_ms=100.0, out=None):
+    """(y, envelope) of stage 2 on one channel"""
+    x = f32(x)
+    y, e = _fx_out(x, out), np.zeros_like(x)
+    _fx_host("fx_compressor_host", lib().rvcx_fx_compressor_host(x.ctypes.data, x.shape[0], int(sr), float(ratio),
+                                                                 float(threshold_db), float(attack_ms), float(release_ms),
+                                                                 y.ctypes.data, e.ctypes.data))
+    return y, e
+
+
+def fx_gate_host(x, sr, threshold_db, ratio, attack_ms, release_ms, out=None):
+    """(y, envelope) of stage 3 on one channel"""
+    x = f32(x)
+    y, e = _fx_out(x, out), np.zeros_like(x)
+    _fx_host("fx_gate_host", lib().rvcx_fx_gate_host(x.ctypes.data, x.shape[0], int(sr), float(threshold_db), float(ratio),
+                                                     float(attack_ms), float(release_ms), y.ctypes.data, e.ctypes.data))
+    return y, e
+
+
+def fx_comb_host(x, D, fb, d):
+    x = f32(x)
+    y = np.empty_like(x)
+    _fx_host("fx_comb_host", lib().rvcx_fx_comb_host(x.ctypes.data, x.shape[0], int(D), float(fb), float(d), y.ctypes.data))
+    return y
+
+
+def fx_allpass_host(x, D):
+    x = f32(x)
+    y = np.empty_like(x)
+    _fx_host("fx_allpass_host", lib().rvcx_fx_allpass_host(x.ctypes.data, x.shape[0], int(D), y.ctypes.data))
+    return y
+
+
+def fx_chorus_host(x, sr, rate_hz, depth, centre_delay_ms, feedback, mix, out=None):
+    x = f32(x)
+    y = _fx_out(x, out)
+    _fx_host("fx_chorus_host", lib().rvcx_fx_chorus_host(x.ctypes.data, x.shape[0], int(sr), float(rate_hz), float(depth),
+                                                         float(centre_delay_ms), float(feedback), float(mix), y.ctypes.data))
+    return y
+
+
+def _stereo_i16(a, what):
+    a = np.ascontiguousarray(a)
+    if a.dtype != np.int16 or a.ndim != 2 or a.shape[1] != 2:
+        raise RvcxError(f"{what}: int16 array of shape (frames, 2) expected")
+    return a
+
+
+def fx_mix_host(vocal, inst, vocal_gain_db=0.0, inst_gain_db=0.0, out=None):
+    v, m = _stereo_i16(vocal, "fx_mix_host"), _stereo_i16(inst, "fx_mix_host")
+    y = _fx_out(v, out)
+    _fx_host("fx_mix_host", lib().rvcx_fx_mix_host(v.ctypes.data, v.shape[0], m.ctypes.data, m.shape[0], float(vocal_gain_db),
+                                                   float(inst_gain_db), y.ctypes.data))
+    return y
 
 
 _device_info_cache = {}
@@ -1227,6 +1392,92 @@ class Context:
         y = np.empty(max(n_out, 0), np.float64)
         self._ck(lib().rvcx_resample_f64_kind(self._h, _p(a, C.c_double), C.c_int64(frames), ch, int(sr_in), int(sr_out),
                                               int(kind), _p(y, C.c_double)), "resample_f64")
+        return y
+
+    # ---- post-production (rvcx.h "post-production"): signals are float32 (frames,) or (frames, channels) -------------------
+    @staticmethod
+    def _fx_in(x):
+        x = f32(x)
+        if x.ndim not in (1, 2) or x.shape[0] < 1:
+            raise RvcxError("fx: array of shape (frames,) or (frames, channels) with at least one frame expected")
+        return x, (1 if x.ndim == 1 else x.shape[1])
+
+    def fx_chain(self, items, params: "FxParams"):
+        """rvcx_fx_chain: the whole board on a list of (frames, 2) float32 arrays in one call -> list of arrays"""
+        xs = [self._fx_in(x)[0] for x in items]
+        for x in xs:
+            if (1 if x.ndim == 1 else x.shape[1]) != params.channels:
+                raise RvcxError("fx_chain: every item needs params.channels channels")
+        ys = [np.empty_like(x) for x in xs]
+        B = len(xs)
+        xp = (C.c_void_p * max(B, 1))(*[x.ctypes.data for x in xs])
+        yp = (C.c_void_p * max(B, 1))(*[y.ctypes.data for y in ys])
+        n = (C.c_int64 * max(B, 1))(*[x.shape[0] for x in xs])
+        self._ck(lib().rvcx_fx_chain(self._h, B, xp, n, C.byref(params), yp), "fx_chain")
+        return ys
+
+    def fx_last_passes(self):
+        """({compressor, gate x^2 follower, gate peak follower} relaxation passes, groups) of the last post-production call"""
+        p = (C.c_int32 * 3)()
+        g = lib().rvcx_fx_last_passes(self._h, p)
+        return [int(v) for v in p], int(g)
+
+    def fx_last_timing(self):
+        """per-stage device ms of the last fx_chain call (rvcx_last_timing's nine slots under their post-production names)"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "copies", "total"]
+        return dict(zip(names, [float(v) for v in ms]))
+
+    def fx_highpass(self, x, sr, fc=50.0):
+        x, ch = self._fx_in(x)
+        y = np.empty_like(x)
+        self._ck(lib().rvcx_op_fx_highpass(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(fc), y.ctypes.data), "op_fx_highpass")
+        return y
+
+    def fx_compressor(self, x, sr, ratio, threshold_db, attack_ms=1.0, release_ms=100.0, want_env=False):
+        x, ch = self._fx_in(x)
+        y, e = np.empty_like(x), (np.zeros_like(x) if want_env else None)
+        self._ck(lib().rvcx_op_fx_compressor(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(ratio), float(threshold_db),
+                                             float(attack_ms), float(release_ms), y.ctypes.data,
+                                             None if e is None else e.ctypes.data), "op_fx_compressor")
+        return (y, e) if want_env else y
+
+    def fx_gate(self, x, sr, threshold_db, ratio, attack_ms, release_ms, want_env=False):
+        x, ch = self._fx_in(x)
+        y, e = np.empty_like(x), (np.zeros_like(x) if want_env else None)
+        self._ck(lib().rvcx_op_fx_gate(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(threshold_db), float(ratio),
+                                       float(attack_ms), float(release_ms), y.ctypes.data,
+                                       None if e is None else e.ctypes.data), "op_fx_gate")
+        return (y, e) if want_env else y
+
+    def fx_reverb(self, x, sr, room_size, damping, wet, dry, width):
+        x, ch = self._fx_in(x)
+        y = np.empty_like(x)
+        self._ck(lib().rvcx_op_fx_reverb(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(room_size), float(damping),
+                                         float(wet), float(dry), float(width), y.ctypes.data), "op_fx_reverb")
+        return y
+
+    def fx_shelf(self, x, sr, gain_db, high=False, fc=440.0, Q=2.0 ** -0.5):
+        x, ch = self._fx_in(x)
+        y = np.empty_like(x)
+        self._ck(lib().rvcx_op_fx_shelf(self._h, x.ctypes.data, x.shape[0], ch, int(sr), int(bool(high)), float(gain_db),
+                                        float(fc), float(Q), y.ctypes.data), "op_fx_shelf")
+        return y
+
+    def fx_chorus(self, x, sr, rate_hz, depth, centre_delay_ms, feedback, mix):
+        x, ch = self._fx_in(x)
+        y = np.empty_like(x)
+        self._ck(lib().rvcx_op_fx_chorus(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(rate_hz), float(depth),
+                                         float(centre_delay_ms), float(feedback), float(mix), y.ctypes.data), "op_fx_chorus")
+        return y
+
+    def fx_mix(self, vocal, inst, vocal_gain_db=0.0, inst_gain_db=0.0):
+        """rvcx_op_fx_mix: (n_v, 2) and (n_i, 2) int16 -> (n_v, 2) int16"""
+        v, m = _stereo_i16(vocal, "fx_mix"), _stereo_i16(inst, "fx_mix")
+        y = np.empty_like(v)
+        self._ck(lib().rvcx_op_fx_mix(self._h, v.ctypes.data, v.shape[0], m.ctypes.data, m.shape[0], float(vocal_gain_db),
+                                      float(inst_gain_db), y.ctypes.data), "op_fx_mix")
         return y
 
     def vc_frames(self, n: int) -> int:

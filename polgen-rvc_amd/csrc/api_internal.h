@@ -110,6 +110,8 @@ struct rvcx_ctx {
   std::deque<rvcx::api::TicketPtr> inflight;                          // submit order; at most two
   std::unordered_map<rvcx_ticket, rvcx::api::TicketPtr> tickets;      // every ticket that has not been waited for
   std::deque<std::pair<rvcx_ticket, float>> leads;         // lead_ms of the tickets waited for last
+  int fx_passes[3] = {0, 0, 0};   // rvcx_fx_last_passes: relaxation passes of the last post-production call's followers
+  int fx_groups = 0;              // and the groups it ran in
   rvcx::Arena load_arena;     // rvcx_resample_f64* with tickets in flight: a buffer nobody else uses (see there)
 };
 namespace rvcx {

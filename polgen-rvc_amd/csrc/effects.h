@@ -1,0 +1,70 @@
+// Post-production (include/rvcx.h "post-production"): the vocal effects chain and the cover mix.  effects.hip holds the
+// kernels, their launchers, the coefficient formulas and the sequential host twins; api_fx.hip the entry points.
+//
+// Device layout: planar rows.  Row r = item * C + channel holds len[r] samples at the front of ld floats (ld a multiple of
+// kFxChunk, the tail zero).  Every kernel takes one row per blockIdx.y and cuts it into chunks counted from the row's first
+// sample, so a row's result depends on nothing but the row (and, for the reverb, its partner).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+namespace rvcx {
+
+constexpr int kFxChunk = 1024;       // samples a lane walks alone in the scan and follower kernels (rvcx_fx_chunk)
+
+struct FxBiquad {                    // normalised by a0; transposed direct form II
+  float b0, b1, b2, a1, a2;
+};
+// kind 0: the first-order high-pass of stage 1 (b2 = a2 = 0), 1: low shelf, 2: high shelf (audio-EQ-cookbook, rvcx.h)
+FxBiquad fx_coeffs(int kind, int sr, double fc, double Q, double gain_db);
+float fx_cte(double ms, int sr);                         // exp(-2 pi 1000 / (ms sr)), 0 below 1e-3 ms
+inline int fx_delay(int sr, int D) { return (int)((int64_t)sr * D / 44100); }
+inline bool fx_rate_ok(int sr) { return sr >= 8000 && sr <= 192000 && sr % 100 == 0; }
+
+struct FxReverb {                    // what the three reverb kernels need, formed on the host in double, rounded once
+  int comb[2][8], ap[2][4];          // delays in samples per side
+  float fb, d, omd;                  // feedback, damping d and 1 - d
+  float w1, w2, dry2;                // 1.5 wet (1 + width), 1.5 wet (1 - width), 2 dry
+};
+FxReverb fx_reverb_setup(int sr, double room, double damping, double wet, double dry, double width);
+
+struct FxChorus {
+  double w, srk, centre, dep10;      // 2 pi rate / sr, sr / 1000, centre delay in ms, 10 depth
+  float fb, mix, omm;                // feedback, mix and 1 - mix
+  int T;                             // floor(tau_min) - 1: samples of one row that do not depend on each other
+};
+FxChorus fx_chorus_setup(int sr, double rate, double depth, double centre_ms, double feedback, double mix);
+
+// ---- launchers (all on stream s; R rows, ld floats apart; len: R ints on the device) -----------------------------------
+// stage (item b: n[b] frames of C interleaved floats at b * ld * C) <-> planar rows; the planar tail [len, ld) is zeroed
+void launch_fx_deinterleave(const float* stage, float* rows, const int* len, int B, int C, long ld, hipStream_t s);
+void launch_fx_interleave(const float* rows, float* stage, const int* len, int B, int C, long ld, hipStream_t s);
+// y = biquad(x) per row: zero-state chunk responses, one carry scan per row, the chunks again from their true states.
+// scratch: 2 * R * (ld / kFxChunk) float2
+void launch_fx_biquad(const FxBiquad& q, const float* x, float* y, const int* len, int R, long ld, float* scratch,
+                      hipStream_t s);
+// env = follower(|x| or x^2) per row (rvcx.h), by relaxation over chunks; returns the passes that ran a chunk.
+// state: 3 * R * (ld / kFxChunk) floats + 64 ints.  Synchronises s once per pass.
+int launch_fx_follower(const float* x, float* env, const int* len, const int* len_host, int R, long ld, int square,
+                       int sqrt_out, float c_att, float c_rel, float* state, hipStream_t s);
+// y = x * g(env): gate = 0 the compressor's gain, 1 the noise gate's; thr linear, expo the exponent of e / thr
+void launch_fx_gain(const float* x, const float* env, float* y, int R, long ld, int gate, float thr, float expo, hipStream_t s);
+// Freeverb on stereo items (rows 2 b, 2 b + 1): combs (B * 2 * 8 rows of ld) -> ap (B * 2 rows) -> y
+void launch_fx_reverb(const FxReverb& rv, const float* x, float* combs, float* ap, float* y, const int* len, int B, long ld,
+                      hipStream_t s);
+// d: R rows of ld floats of scratch (the delay line; unused when feedback == 0)
+void launch_fx_chorus(const FxChorus& ch, const float* x, float* d, float* y, const int* len, int R, long ld, hipStream_t s);
+// out[i] = sat(gain(v[i]) + gain(inst[i] or 0)): nv / ni interleaved int16 samples
+void launch_fx_mix(const int16_t* v, long nv, const int16_t* inst, long ni, double gv, double gi, int16_t* out, hipStream_t s);
+
+// ---- sequential float32 twins on the host ------------------------------------------------------------------------------
+void fx_highpass_host(const FxBiquad& q, const float* x, long n, float* y);
+void fx_biquad_host(const FxBiquad& q, const float* x, long n, float* y);
+void fx_follower_host(const float* x, long n, int square, int sqrt_out, float c_att, float c_rel, float* env);
+void fx_gain_host(const float* x, const float* env, long n, int gate, float thr, float expo, float* y);
+void fx_comb_host(const float* in, long n, int D, float fb, float d, float* out);
+void fx_allpass_host(const float* in, long n, int D, float* out);
+void fx_chorus_host(const FxChorus& ch, const float* x, long n, float* y);
+void fx_mix_host(const int16_t* v, long nv, const int16_t* inst, long ni, double gv, double gi, int16_t* out);
+
+}  // namespace rvcx

@@ -1,0 +1,154 @@
+"""Drop-in mirror of ``rvc/scripts/audio_processing.py`` (the "processing" tab): ``convert_to_stereo`` -> ``add_effects`` ->
+``combine_audio``, with the reference's positional signatures and return values.
+
+The reference runs a pedalboard board one second at a time on the CPU and mixes with pydub.  Here the board is
+``rvcx_fx_chain`` and the mix ``rvcx_op_fx_mix`` on the resident context (``infer/_state.py``); the arithmetic of every stage
+is defined in include/rvcx.h ("post-production").  Neither pedalboard nor pydub is part of the reference tree: parity with
+their classes is unpinned, the definitions are what is tested.  Files are read and written through ``infer/audio.py``: "wav"
+and "flac" outputs work, any other ``output_format`` ("mp3", the tab's default, "m4a", ...) raises ``ValueError`` naming the
+missing encoder before any work is done.  ``progress`` is accepted and ignored.
+
+``process_audio_many(jobs)`` is new: a list of covers whose boards run in ONE ``rvcx_fx_chain`` call per (rate, settings).
+"""
+from __future__ import annotations
+
+import os
+import tempfile
+
+import numpy as np
+
+from .. import _lib
+from ..infer import _state
+from ..infer.audio import convert_to_stereo, read_audio, write_output, write_wav_pcm16
+
+__all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "OUTPUT_DIR"]
+
+OUTPUT_DIR = os.path.join(os.getcwd(), "output")
+
+_FORMATS = ("wav", "flac")
+
+
+def _check_format(output_format):
+    if str(output_format).lower() not in _FORMATS:
+        raise ValueError(f"output format {output_format!r}: this installation has no encoder for it (pydub's ffmpeg is not "
+                         f"installed); the formats written here are {', '.join(_FORMATS)}")
+
+
+def _stereo(a):
+    """(frames,) or (frames, channels) -> (frames, 2): mono doubled, the first two channels otherwise"""
+    a = np.asarray(a)
+    if a.ndim == 1:
+        return np.stack([a, a], axis=1)
+    return np.ascontiguousarray(a[:, :2]) if a.shape[1] >= 2 else np.repeat(a, 2, axis=1)
+
+
+def _pcm16(a):
+    """read_audio's float64 -> the int16 samples pydub holds (a 16-bit file comes back exactly)"""
+    return np.clip(np.rint(np.asarray(a, np.float64) * 32768.0), -32768, 32767).astype(np.int16)
+
+
+def _effects(ctx, signals, sr, values):
+    """the board on a list of (frames, 2) float arrays of one rate and one setting: one rvcx_fx_chain call"""
+    params = _lib.FxParams.make(values, sr, 2)
+    with ctx.lock:
+        return ctx.fx_chain([np.ascontiguousarray(_stereo(x), dtype=np.float32) for x in signals], params)
+
+
+def combine_audio(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain, output_format):
+    """audio_processing.py:29-40: vocal + gain overlaid with instrumental + gain in int16, at the vocal's rate and length"""
+    _check_format(output_format)
+    ctx = _state.context()
+    v, sr = read_audio(vocal_path)
+    m, sr_m = read_audio(instrumental_path)
+    v, m = _stereo(v), _stereo(m)
+    with ctx.lock:
+        if sr_m != sr:
+            m = np.stack([ctx.resample(m[:, c], sr_m, sr) for c in range(2)], axis=1)
+        out = ctx.fx_mix(_pcm16(v), _pcm16(m), vocal_gain, instrumental_gain)
+    write_output(output_path, out, sr)       # FLAC for a path ending in ".flac", WAV bytes otherwise
+
+
+def add_effects(vocal_path, output_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping, reverb_width,
+                low_shelf_gain, high_shelf_gain, compressor_ratio, compressor_threshold, noise_gate_threshold,
+                noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz, chorus_depth,
+                chorus_centre_delay_ms, chorus_feedback, chorus_mix):
+    """audio_processing.py:54-109: the board on one file, written as a stereo 16-bit WAV"""
+    values = (reverb_rm_size, reverb_wet, reverb_dry, reverb_damping, reverb_width, low_shelf_gain, high_shelf_gain,
+              compressor_ratio, compressor_threshold, noise_gate_threshold, noise_gate_ratio, noise_gate_attack,
+              noise_gate_release, chorus_rate_hz, chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix)
+    x, sr = read_audio(vocal_path)
+    y = _effects(_state.context(), [x], sr, values)[0]
+    write_wav_pcm16(output_path, y, sr)
+
+
+def _check_paths(vocal_audio_path, instrumental_audio_path):
+    if not vocal_audio_path:
+        raise ValueError(
+            "Не удалось найти аудиофайл с вокалом. "
+            "Убедитесь, что файл загрузился или проверьте правильность пути к нему."
+        )
+    if not instrumental_audio_path:
+        raise ValueError(
+            "Не удалось найти аудиофайл с инструменталом. "
+            "Убедитесь, что файл загрузился или проверьте правильность пути к нему."
+        )
+
+
+def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping,
+                  reverb_width, low_shelf_gain, high_shelf_gain, compressor_ratio, compressor_threshold,
+                  noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
+                  chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix, output_format, vocal_gain,
+                  instrumental_gain, use_effects, progress=None):
+    """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>"""
+    _check_paths(vocal_audio_path, instrumental_audio_path)
+    _check_format(output_format)
+    os.makedirs(OUTPUT_DIR, exist_ok=True)
+    voice_stereo_path = os.path.join(OUTPUT_DIR, "Voice_Stereo.wav")
+    aicover_path = os.path.join(OUTPUT_DIR, f"AiCover.{output_format}")
+    if os.path.exists(aicover_path):
+        os.remove(aicover_path)
+    convert_to_stereo(vocal_audio_path, voice_stereo_path)
+    if use_effects:
+        vocal_output_path = os.path.join(OUTPUT_DIR, "Vocal_Effected.wav")
+        add_effects(voice_stereo_path, vocal_output_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping,
+                    reverb_width, low_shelf_gain, high_shelf_gain, compressor_ratio, compressor_threshold,
+                    noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
+                    chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix)
+    else:
+        vocal_output_path = voice_stereo_path
+    combine_audio(vocal_output_path, instrumental_audio_path, aicover_path, vocal_gain, instrumental_gain, output_format)
+    return aicover_path
+
+
+def process_audio_many(jobs):
+    """A list of covers in one go.  Every job is the positional argument tuple of ``process_audio`` (24 values; a 25th, when
+    given, is the output path -- the default is OUTPUT_DIR/AiCover_<index>.<output_format>).  The boards of all jobs that
+    share a sample rate and the eighteen effect values run in ONE rvcx_fx_chain call; every cover is byte for byte what
+    ``process_audio`` writes for the same arguments.  Returns the list of output paths."""
+    jobs = [tuple(j) for j in jobs]
+    for j in jobs:
+        if len(j) not in (24, 25):
+            raise ValueError("process_audio_many: a job is the 24 positional arguments of process_audio (+ an output path)")
+        _check_paths(j[0], j[1])
+        _check_format(j[20])
+    os.makedirs(OUTPUT_DIR, exist_ok=True)
+    ctx = _state.context()
+    outs = [j[24] if len(j) == 25 else os.path.join(OUTPUT_DIR, f"AiCover_{i}.{j[20]}") for i, j in enumerate(jobs)]
+    with tempfile.TemporaryDirectory(prefix="rvcx_fx_") as tmp:
+        vocal, groups = [], {}
+        for i, j in enumerate(jobs):
+            vocal.append(os.path.join(tmp, f"Voice_Stereo_{i}.wav"))
+            convert_to_stereo(j[0], vocal[i])
+            if j[23]:
+                x, sr = read_audio(vocal[i])
+                groups.setdefault((sr, tuple(float(v) for v in j[2:20])), []).append((i, x))
+        for (sr, values), members in groups.items():
+            ys = _effects(ctx, [x for _, x in members], sr, values)
+            for (i, _), y in zip(members, ys):
+                vocal[i] = os.path.join(tmp, f"Vocal_Effected_{i}.wav")
+                write_wav_pcm16(vocal[i], y, sr)
+        for i, j in enumerate(jobs):
+            if os.path.exists(outs[i]):
+                os.remove(outs[i])
+            combine_audio(vocal[i], j[1], outs[i], j[21], j[22], j[20])
+    return outs

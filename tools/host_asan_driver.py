@@ -192,4 +192,37 @@ for cut in (10, 50, len(blob) // 2, len(blob) - 3):
         _lib.flac_decode(blob[:cut])
     except _lib.RvcxError:
         pass
+# ---- post-production: the host twins are the product's arithmetic on the host; the chain's planning, grouping and copies run
+# on the stub (launches are no-ops there, so every follower settles in its first pass)
+g = np.random.Generator(np.random.PCG64(6))
+x = (0.3 * g.standard_normal(3000)).astype(np.float32)
+for sr in (8000, 192000):
+    _lib.fx_highpass_host(x, sr)
+    _lib.fx_biquad_host(x, _lib.fx_coeffs(2, sr, 440.0, 2.0 ** -0.5, 6.0))
+    _lib.fx_compressor_host(x, sr, 4.0, -12.0)
+    _lib.fx_gate_host(x, sr, -40.0, 8.0, 10.0, 100.0)
+    _lib.fx_comb_host(x, _lib.fx_delay(sr, 1617 + 23), 0.84, 0.2)
+    _lib.fx_allpass_host(x, _lib.fx_delay(sr, 225))
+    _lib.fx_chorus_host(x, sr, 1.5, 0.25, 7.0, 0.5, 0.5)
+for n in (0, 1, 7):
+    _lib.fx_comb_host(x[:n], 5, 0.5, 0.2), _lib.fx_allpass_host(x[:n], 5), _lib.fx_chorus_host(x[:n], 8000, 1.0, 0.1, 2.0, 0.3, 0.5)
+v = g.integers(-32768, 32768, (100, 2)).astype(np.int16)
+for n_i in (0, 40, 100, 300):
+    _lib.fx_mix_host(v, g.integers(-32768, 32768, (n_i, 2)).astype(np.int16), 6.0, -3.0)
+ctx = _lib.Context(0)
+items = [np.zeros((n, 2), np.float32) for n in (1, 150, 1024, 5000)]
+fxp = _lib.FxParams.make(dict(_lib.FX_UI_DEFAULTS, chorus_mix=0.5, chorus_feedback=0.3, chorus_centre_delay_ms=7.0,
+                              low_shelf_gain=3.0, high_shelf_gain=-3.0), 8000, 2)
+os.environ["RVCX_MAX_BATCH"] = "3"
+assert [y.shape for y in ctx.fx_chain(items, fxp)] == [a.shape for a in items] and ctx.fx_last_passes()[1] == 2
+del os.environ["RVCX_MAX_BATCH"]
+ctx.fx_compressor(items[3][:, 0], 8000, 4.0, -12.0, want_env=True)
+ctx.fx_mix(v, v[:30], 0.0, 0.0)
+for bad in (lambda: ctx.fx_reverb(items[1][:, 0], 8000, 0.1, 0.9, 0.1, 0.8, 1.0), lambda: ctx.fx_chorus(items[1], 8000, 1, 0.2, 7, 1.0, 0.5),
+            lambda: ctx.fx_highpass(items[1], 22050), lambda: _lib.fx_gate_host(x, 8000, -40.0, 0.5, 10.0, 100.0)):
+    try:
+        bad()
+    except _lib.RvcxError:
+        pass
+ctx.close()
 print("HOST_ASAN_OK launches", int(L.hipstub_launches()) if hasattr(L, "hipstub_launches") else -1)
