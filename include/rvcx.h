@@ -588,6 +588,68 @@ int rvcx_fx_chorus_host(const float* x, int64_t n, int sr, float rate_hz, float 
 int rvcx_fx_mix_host(const int16_t* vocal, int64_t n_v, const int16_t* inst, int64_t n_i, float vocal_gain_db,
                      float inst_gain_db, int16_t* out);
 
+/* ---- live post-production ---------------------------------------------------------------------------------------------
+ * The board of "post-production" inside a live-stream session: rvcx_stream_open_fx puts stages 1 - 7 behind the output
+ * resampler, inside the step, on the device, with all state carried from block to block.
+ *
+ * Signal.  For stream s, v = everything the session has emitted since open or reset at the delivery rate sr (out_rate when the
+ * output is resampled, else the voice model's rate), the zeros of the output resampler's delay included, duplicated to stereo
+ * (L = R, as convert_to_stereo does).  Output.  A session with effects returns stages 1 - 7 (the definitions above, in the
+ * board's order) applied to v from zero state at sample 0 of the session, stereo interleaved (frames, 2); step k returns
+ * samples [k Bout, (k + 1) Bout) of that result.  The board adds no delay.  Identity stages follow the rule above (ratio == 1,
+ * 0 dB and mix == 0 are skipped; the high-pass and the reverb never are).  The chorus' tau(n) takes the global sample index n =
+ * step counter x block (int64, restarting at 0 on reset); there is no device counter.
+ *
+ * Arithmetic -- what makes the result independent of the cut.  Every stage runs in sample order, every rounding is one IEEE
+ * operation (contraction off), and the step functions are those of the one-shot kernels and host twins (csrc/effects_device.h):
+ *  - high-pass, low shelf, high shelf: the float32 transposed-direct-form-II recurrence sample by sample, (s1, s2) carried.
+ *    Equal to rvcx_fx_highpass_host / rvcx_fx_biquad_host on the whole signal BIT FOR BIT.  Deliberately not the one-shot
+ *    kernels' bits: their chunked scan carries the state in double and associates by the row's length.
+ *  - compressor, gate: the followers in sample order with e (and the gate's r) carried, the one-shot device gain.  Equal to
+ *    rvcx_op_fx_compressor / rvcx_op_fx_gate on the whole signal bit for bit (the envelopes thereby to rvcx_fx_follower_host).
+ *  - reverb: per comb o = buf[i]; last = fma(last, d, o (1 - d)); buf[i] = fma(last, fb, in); the comb outputs summed in the
+ *    listed order; the four all-passes in series; the mix FMAs of stage 4.  1 - d is (float)(1 - (double)(float)d), the comb
+ *    twin's.  Equal to rvcx_fx_reverb_host (below) on the whole signal bit for bit; not to rvcx_op_fx_reverb, whose 64-lane
+ *    scan re-associates the damping one-pole.
+ *  - chorus: the one-shot tap (fx_chorus_tap) at the global index.  Equal to rvcx_op_fx_chorus on the whole signal bit for
+ *    bit, for feedback == 0 and != 0.
+ * So live and one-shot results differ in the last bits for the linear stages and the reverb, and only there.
+ *
+ * Rates.  sr a multiple of 100 Hz in 8000 .. 192000; 3200 .. 7900 too, but only when the voice model's own rate is below 8000
+ * (the reduced test models' 4800 / 6000 Hz; the concession rvcx_stream_open_io makes -- at 4800 Hz the comb delays are 121 ..,
+ * the shortest all-pass 24, the chorus block 20).  Anything else is refused at open, with a message.
+ *
+ * State.  Per stream: the biquad and follower states, 16 comb lines with their one-pole states, 8 all-pass lines, and per
+ * channel a chorus ring of sr + 2 samples (the 1000 ms the board accepts) + two blocks.  Lines and rings are indexed by the
+ * global sample index mod their length; there are no stored positions, and a block may be shorter than every delay.  All of
+ * it is the session's own memory and exists twice: a step reads set cur and writes the other one, and the sets change places
+ * only when the step has succeeded (ring, carry, FIFOs).  The board adds no host synchronisation to a step.  rvcx_last_timing
+ * counts it in the last interval ("SOLA + copies").  rvcx_stream_reset zeroes it; rvcx_stream_close and rvcx_destroy free it. */
+/* fx == NULL: rvcx_stream_open_io, launch for launch.  fx->sample_rate must be 0 or the delivery rate, fx->channels 0 or 2; the
+ * refusals of rvcx_fx_chain (ratio < 1, |feedback| >= 1, a value that is not finite, ...) are made here, and nothing is opened */
+int rvcx_stream_open_fx(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_stream_io*, const rvcx_fx_params* fx,
+                        const rvcx_params* p, const int32_t* sid, const float* pitch, int* stream_id);
+/* 1, or 2 for a session with effects: out_hd[s] of a step holds rvcx_stream_out_len x channels floats.  pre_sola_hd, offsets
+ * and rvcx_stream_last_taps keep their meaning: mono, in front of the board */
+int rvcx_stream_out_channels(rvcx_ctx*, int stream_id);
+/* new parameters from the next step on.  All state is kept (a reverb tail rings on), except that the state of a stage the new
+ * values make an identity is zeroed once, in both sets: it starts clean when it comes back.  A refused value: -1, nothing
+ * changed.  Refused on a session opened without effects (its channel count is fixed at open).  No parameter smoothing. */
+int rvcx_stream_set_fx(rvcx_ctx*, int stream_id, const rvcx_fx_params*);
+/* device ms of the board in the last step: {high-pass (with the load), compressor, gate, reverb, low shelf, high shelf,
+ * chorus (with the interleave), total} */
+int rvcx_stream_last_fx_ms(rvcx_ctx*, int stream_id, float* ms8);
+/* the session's board without a session and without a model: S rows of `frames` input frames (x_hd: S x frames x channels,
+ * channels 1 or 2, interleaved), cut into blocks of block_frames 10 ms frames (frames must be a multiple of block_frames * sr /
+ * 100), through the same state and kernel code a session runs per step; y_hd receives S x frames x 2.  stage_mask bit i enables
+ * stage i + 1; a disabled stage is skipped like an identity.  sr: the rule above, 3200 .. 7900 allowed */
+int rvcx_op_stream_fx(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int channels, int sr, int block_frames,
+                      const rvcx_fx_params* fx, uint32_t stage_mask, float* y_hd);
+/* host only, no context: stage 4 on one stereo item, x (n, 2) -> y (n, 2), sequentially in float32 from rvcx_fx_comb_host /
+ * rvcx_fx_allpass_host and the mix FMAs; sr as the other host twins.  -1 and nothing written for arguments out of range */
+int rvcx_fx_reverb_host(const float* x, int64_t n, int sr, float room_size, float damping, float wet, float dry, float width,
+                        float* y);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:

@@ -164,6 +164,8 @@ SYMBOLS = [
     "rvcx_stream_out_len", "rvcx_stream_noise_len", "rvcx_stream_frames",
     "rvcx_stream_open_io", "rvcx_stream_in_len", "rvcx_stream_delays", "rvcx_stream_resample_delay", "rvcx_stream_last_taps",
     "rvcx_stream_set", "rvcx_op_stream_resample",
+    "rvcx_stream_open_fx", "rvcx_stream_out_channels", "rvcx_stream_set_fx", "rvcx_stream_last_fx_ms", "rvcx_op_stream_fx",
+    "rvcx_fx_reverb_host",
     "rvcx_fx_chain", "rvcx_op_fx_highpass", "rvcx_op_fx_compressor", "rvcx_op_fx_gate", "rvcx_op_fx_reverb", "rvcx_op_fx_shelf",
     "rvcx_op_fx_chorus", "rvcx_op_fx_mix", "rvcx_fx_chunk", "rvcx_fx_last_passes", "rvcx_fx_cte", "rvcx_fx_delay",
     "rvcx_fx_coeffs", "rvcx_fx_highpass_host", "rvcx_fx_biquad_host", "rvcx_fx_follower_host", "rvcx_fx_compressor_host",
@@ -260,6 +262,12 @@ def lib() -> C.CDLL:
         _lib.rvcx_fx_allpass_host.argtypes = [vp, i64, i, vp]
         _lib.rvcx_fx_chorus_host.argtypes = [vp, i64, i, f, f, f, f, f, vp]
         _lib.rvcx_fx_mix_host.argtypes = [vp, i64, vp, i64, f, f, vp]
+        _lib.rvcx_fx_reverb_host.argtypes = [vp, i64, i, f, f, f, f, f, vp]
+        _lib.rvcx_stream_open_fx.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_stream_out_channels.argtypes = [vp, i]
+        _lib.rvcx_stream_set_fx.argtypes = [vp, i, vp]
+        _lib.rvcx_stream_last_fx_ms.argtypes = [vp, i, vp]
+        _lib.rvcx_op_stream_fx.argtypes = [vp, vp, i, i64, i, i, i, vp, C.c_uint32, vp]
     return _lib
 
 
@@ -354,6 +362,31 @@ def fx_chorus_host(x, sr, rate_hz, depth, centre_delay_ms, feedback, mix, out=No
     _fx_host("fx_chorus_host", lib().rvcx_fx_chorus_host(x.ctypes.data, x.shape[0], int(sr), float(rate_hz), float(depth),
                                                          float(centre_delay_ms), float(feedback), float(mix), y.ctypes.data))
     return y
+
+
+def fx_reverb_host(x, sr, room_size, damping, wet, dry, width):
+    """rvcx_fx_reverb_host: stage 4 on one stereo item (n, 2), sequentially in float32 -- what a live session's reverb
+    equals bit for bit"""
+    x = f32(x)
+    if x.ndim != 2 or x.shape[1] != 2:
+        raise RvcxError("fx_reverb_host: a stereo item of shape (frames, 2) expected")
+    y = np.empty_like(x)
+    _fx_host("fx_reverb_host", lib().rvcx_fx_reverb_host(x.ctypes.data, x.shape[0], int(sr), float(room_size), float(damping),
+                                                         float(wet), float(dry), float(width), y.ctypes.data))
+    return y
+
+
+def fx_values(effects, base=None) -> dict:
+    """the eighteen add_effects values as a dict: `effects` (a dict of some of them, or an FxParams) laid over `base`
+    (FX_UI_DEFAULTS when None).  An unknown name is refused."""
+    if isinstance(effects, FxParams):
+        return {k: float(getattr(effects, k)) for k in FX_FIELDS}
+    out = dict(FX_UI_DEFAULTS if base is None else base)
+    unknown = sorted(set(effects) - set(FX_FIELDS))
+    if unknown:
+        raise RvcxError(f"effects: unknown name(s) {unknown}; the names are those of add_effects: {list(FX_FIELDS)}")
+    out.update({k: float(v) for k, v in effects.items()})
+    return out
 
 
 def _stereo_i16(a, what):
@@ -547,7 +580,9 @@ class StreamSession:
         self.n_streams = int(cfg.n_streams)
         self.in_channels = int(io.in_channels)
         self.block_in = int(lib().rvcx_stream_in_len(ctx._h, sid))        # frames per block at the input rate
-        self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))      # samples per block as step() returns them
+        self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))      # frames per block as step() returns them
+        self.out_channels = int(lib().rvcx_stream_out_channels(ctx._h, sid))   # 2 when the effects board is on
+        self.effects = None                                               # the eighteen values in force (a dict), or None
         self.noise_len = int(lib().rvcx_stream_noise_len(ctx._h, sid))
         self.frames = int(lib().rvcx_stream_frames(ctx._h, sid))          # T of the TextEncoder
         din, dout = C.c_int32(0), C.c_int32(0)
@@ -565,7 +600,8 @@ class StreamSession:
         self.latency_ms = 1e3 * self.in_delay / 16000.0 + 1e3 * self.out_delay / float(self.out_rate) + 10.0
 
     def step(self, blocks, noise=None, taps=False):
-        """blocks (S, block_in) float32 -- (S, block_in, in_channels) for in_channels > 1 -- -> (S, block_out) float32.
+        """blocks (S, block_in) float32 -- (S, block_in, in_channels) for in_channels > 1 -- -> (S, block_out) float32,
+        (S, block_out, 2) from a session with effects.
         noise (S, noise_len): parity noise of this step (z_noise then src_noise per stream).  taps=True: (out, pre_sola
         (S, tail_len), offsets (S,)), the latter two at the model's rate."""
         if self.id is None:
@@ -580,7 +616,7 @@ class StreamSession:
             nz = f32(noise)
             if nz.shape != (S, self.noise_len):
                 raise RvcxError(f"StreamSession.step: noise must be ({S}, {self.noise_len})")
-        out = np.empty((S, self.block_out), np.float32)
+        out = np.empty((S, self.block_out) if self.out_channels == 1 else (S, self.block_out, 2), np.float32)
         pre = np.empty((S, self.tail_len), np.float32) if taps else None
         offs = np.empty(S, np.int32) if taps else None
         self._ctx._ck(lib().rvcx_stream_step(self._ctx._h, self.id, self._table(x), self._table(nz), self._table(out),
@@ -614,8 +650,27 @@ class StreamSession:
                                             nan if index_rate is None else float(index_rate),
                                             nan if protect is None else float(protect)), "stream_set")
 
+    def set_effects(self, **changes):
+        """rvcx_stream_set_fx: new values for some of the eighteen add_effects names, applied from the next step on; the others
+        keep their current value.  All state is kept (a reverb tail rings on), except that of a stage the new values turn
+        into an identity.  A refused value changes nothing; a session opened without effects refuses the call."""
+        if self.effects is None:
+            raise RvcxError("StreamSession.set_effects: the session was opened without effects (its channel count is fixed "
+                            "at open)")
+        values = fx_values(changes, self.effects)
+        p = FxParams.make(values, 0, 0)
+        self._ctx._ck(lib().rvcx_stream_set_fx(self._ctx._h, self.id, C.byref(p)), "stream_set_fx")
+        self.effects = values
+
+    def last_fx_ms(self):
+        """per-stage device ms of the board in the last step (rvcx_stream_last_fx_ms)"""
+        ms = (C.c_float * 8)()
+        self._ctx._ck(lib().rvcx_stream_last_fx_ms(self._ctx._h, self.id, ms), "stream_last_fx_ms")
+        names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "total"]
+        return dict(zip(names, [float(v) for v in ms]))
+
     def reset(self):
-        """zero ring, carry and step counter: the session then replays a fresh one"""
+        """zero ring, carry, the board's state and the step counter: the session then replays a fresh one"""
         self._ctx._ck(lib().rvcx_stream_reset(self._ctx._h, self.id), "stream_reset")
 
     def close(self):
@@ -1020,19 +1075,45 @@ class Context:
         return y
 
     def stream_open(self, model_id, params: "Params", sids, pitches, block_frames, context_frames, crossfade_frames,
-                    search_frames, in_rate=0, in_channels=1, out_rate=0) -> "StreamSession":
+                    search_frames, in_rate=0, in_channels=1, out_rate=0, effects=None) -> "StreamSession":
         """rvcx_stream_open_io: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms).  in_rate /
         in_channels: what step() takes (0 or 16000 with one channel: 16 kHz mono); out_rate: what it returns (0 or the
-        model's rate: the model's rate).  With the defaults this is rvcx_stream_open."""
+        model's rate: the model's rate).  effects: a dict of add_effects names laid over FX_UI_DEFAULTS, or an FxParams --
+        the board runs inside every step on what would have left and step() returns stereo (rvcx_stream_open_fx).  With the
+        defaults this is rvcx_stream_open."""
+        values = None if effects is None else fx_values(effects)
         sid, pit = i32(np.atleast_1d(sids)), f32(np.atleast_1d(pitches))
         if sid.ndim != 1 or sid.shape != pit.shape or sid.shape[0] < 1:
             raise RvcxError("stream_open: one speaker id and one pitch per stream")
         cfg = StreamCfg(int(sid.shape[0]), int(block_frames), int(context_frames), int(crossfade_frames), int(search_frames))
         io = StreamIO(int(in_rate), int(in_channels), int(out_rate), 0)
         h = C.c_int(0)
-        self._ck(lib().rvcx_stream_open_io(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(params),
-                                           _p(sid, C.c_int32), _p(pit), C.byref(h)), "stream_open")
-        return StreamSession(self, int(h.value), cfg, io, self.synth_upp(model_id))
+        if values is None:
+            self._ck(lib().rvcx_stream_open_io(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(params),
+                                               _p(sid, C.c_int32), _p(pit), C.byref(h)), "stream_open")
+        else:
+            fx = FxParams.make(values, 0, 0)
+            self._ck(lib().rvcx_stream_open_fx(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(fx), C.byref(params),
+                                               sid.ctypes.data, pit.ctypes.data, C.byref(h)), "stream_open")
+        se = StreamSession(self, int(h.value), cfg, io, self.synth_upp(model_id))
+        se.effects = values
+        return se
+
+    def stream_fx(self, x, sr: int, block_frames: int, params, stages=None) -> np.ndarray:
+        """rvcx_op_stream_fx: a session's effects board without a session.  x (S, frames) or (S, frames, 2) float32, cut into
+        blocks of block_frames * sr / 100 frames and sent through the state and kernels a session runs per step ->
+        (S, frames, 2).  params: a dict of add_effects names laid over FX_UI_DEFAULTS, or an FxParams.  stages: the stage
+        numbers 1 .. 7 to run (None: all); the others are skipped like identities."""
+        x = f32(x)
+        if x.ndim not in (2, 3):
+            raise RvcxError("stream_fx: x must be (S, frames) or (S, frames, channels)")
+        S, frames, ch = x.shape[0], x.shape[1], (1 if x.ndim == 2 else x.shape[2])
+        fx = FxParams.make(fx_values(params), 0, 0)
+        mask = 0x7F if stages is None else sum(1 << (int(k) - 1) for k in set(stages))
+        y = np.empty((S, frames, 2), np.float32)
+        self._ck(lib().rvcx_op_stream_fx(self._h, x.ctypes.data, S, C.c_int64(frames), ch, int(sr), int(block_frames),
+                                         C.byref(fx), mask, y.ctypes.data), "op_stream_fx")
+        return y
 
     def load_rmvpe(self, cfg_struct, state: dict):
         tbl, keep = make_table(state)

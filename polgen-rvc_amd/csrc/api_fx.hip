@@ -5,28 +5,19 @@
 using namespace rvcx;
 using namespace rvcx::api;
 
-namespace {
+namespace rvcx {
+namespace api {
 
-// what one call runs: the chain fills all of it from rvcx_fx_params, a stage-level entry point one stage
-struct FxPlan {
-  int sr = 0, C = 0;
-  bool hp = false, comp = false, gate = false, reverb = false, lo = false, hi = false, chorus = false;
-  double hp_fc = 50.0;
-  double comp_ratio = 1.0, comp_thr_db = 0.0, comp_att = 1.0, comp_rel = 100.0;
-  double gate_thr_db = 0.0, gate_ratio = 1.0, gate_att = 0.0, gate_rel = 0.0;
-  double room = 0.0, damp = 0.0, wet = 0.0, dry = 0.0, width = 0.0;
-  double lo_db = 0.0, hi_db = 0.0, lo_fc = 440.0, hi_fc = 440.0, lo_q = M_SQRT1_2, hi_q = M_SQRT1_2;
-  double rate = 0.0, depth = 0.0, centre = 0.0, fb = 0.0, mix = 0.0;
-};
-
-void fx_check_common(const char* who, int sr, int channels) {
-  if (!fx_rate_ok(sr)) fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
+static void fx_check_common(const char* who, int sr, int channels, bool low_rate) {
+  if (!fx_live_rate_ok(sr, low_rate))
+    fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000" +
+         (low_rate ? " (or 3200 .. 7900 for a reduced-size voice model)" : ""));
   if (channels != 1 && channels != 2) fail(std::string(who) + ": channels must be 1 or 2");
 }
 
 // every refusal of a plan, before anything is written
 void fx_validate(const char* who, const FxPlan& P) {
-  fx_check_common(who, P.sr, P.C);
+  fx_check_common(who, P.sr, P.C, P.low_rate);
   auto finite = [&](double v, const char* what) {
     if (!std::isfinite(v)) fail(std::string(who) + ": " + what + " is not finite");
   };
@@ -59,6 +50,28 @@ void fx_validate(const char* who, const FxPlan& P) {
     if (P.centre < 0.0 || P.centre + 10.0 * std::fabs(P.depth) > 1000.0) fail(std::string(who) + ": the chorus delay must stay inside 0 .. 1000 ms");
   }
 }
+
+FxPlan fx_board_plan(const char* who, const rvcx_fx_params& p, int sr, int channels, bool low_rate) {
+  FxPlan P;
+  P.sr = sr, P.C = channels, P.low_rate = low_rate;
+  P.hp = true;
+  P.comp_ratio = p.compressor_ratio, P.comp_thr_db = p.compressor_threshold, P.comp = true;
+  P.gate_thr_db = p.noise_gate_threshold, P.gate_ratio = p.noise_gate_ratio, P.gate_att = p.noise_gate_attack;
+  P.gate_rel = p.noise_gate_release, P.gate = true;
+  P.reverb = true, P.room = p.reverb_rm_size, P.damp = p.reverb_damping, P.wet = p.reverb_wet, P.dry = p.reverb_dry;
+  P.width = p.reverb_width;
+  P.lo_db = p.low_shelf_gain, P.hi_db = p.high_shelf_gain, P.lo = P.hi = true;
+  P.rate = p.chorus_rate_hz, P.depth = p.chorus_depth, P.centre = p.chorus_centre_delay_ms, P.fb = p.chorus_feedback;
+  P.mix = p.chorus_mix, P.chorus = true;
+  fx_validate(who, P);                  // with every stage on: a refused value is refused whether or not its stage would run
+  P.comp = P.comp_ratio != 1.0, P.gate = P.gate_ratio != 1.0, P.lo = P.lo_db != 0.0, P.hi = P.hi_db != 0.0, P.chorus = P.mix != 0.0;
+  return P;
+}
+
+}  // namespace api
+}  // namespace rvcx
+
+namespace {
 
 size_t fx_item_bytes(const FxPlan& P, long ld) {
   const size_t nch = (size_t)(ld / kFxChunk);
@@ -212,19 +225,7 @@ extern "C" {
 int rvcx_fx_chain(rvcx_ctx* ctx, int B, const float* const* x, const int64_t* n, const rvcx_fx_params* p, float* const* y) {
   API_BEGIN(ctx)
   if (!p) fail("fx_chain: null parameters");
-  FxPlan P;
-  P.sr = p->sample_rate, P.C = p->channels;
-  P.hp = true;
-  P.comp_ratio = p->compressor_ratio, P.comp_thr_db = p->compressor_threshold, P.comp = true;
-  P.gate_thr_db = p->noise_gate_threshold, P.gate_ratio = p->noise_gate_ratio, P.gate_att = p->noise_gate_attack;
-  P.gate_rel = p->noise_gate_release, P.gate = true;
-  P.reverb = true, P.room = p->reverb_rm_size, P.damp = p->reverb_damping, P.wet = p->reverb_wet, P.dry = p->reverb_dry;
-  P.width = p->reverb_width;
-  P.lo_db = p->low_shelf_gain, P.hi_db = p->high_shelf_gain, P.lo = P.hi = true;
-  P.rate = p->chorus_rate_hz, P.depth = p->chorus_depth, P.centre = p->chorus_centre_delay_ms, P.fb = p->chorus_feedback;
-  P.mix = p->chorus_mix, P.chorus = true;
-  fx_validate("fx_chain", P);           // with every stage on: a refused value is refused whether or not its stage would run
-  P.comp = P.comp_ratio != 1.0, P.gate = P.gate_ratio != 1.0, P.lo = P.lo_db != 0.0, P.hi = P.hi_db != 0.0, P.chorus = P.mix != 0.0;
+  const FxPlan P = fx_board_plan("fx_chain", *p, p->sample_rate, p->channels, false);
   fx_run(ctx, C, "fx_chain", B, x, n, P, y, nullptr);
   API_END
 }

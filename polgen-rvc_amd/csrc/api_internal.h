@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "ctx.h"
+#include "effects.h"
 #include "layers.h"
 #include "models.h"
 #include "ops.h"
@@ -55,6 +56,24 @@ struct Ticket {
 };
 using TicketPtr = std::shared_ptr<Ticket>;
 
+// what one call runs: the chain fills all of it from rvcx_fx_params, a stage-level entry point one stage
+struct FxPlan {
+  int sr = 0, C = 0;
+  bool low_rate = false;            // live sessions of reduced-size voice models: 3200 .. 7900 Hz too
+  bool hp = false, comp = false, gate = false, reverb = false, lo = false, hi = false, chorus = false;
+  double hp_fc = 50.0;
+  double comp_ratio = 1.0, comp_thr_db = 0.0, comp_att = 1.0, comp_rel = 100.0;
+  double gate_thr_db = 0.0, gate_ratio = 1.0, gate_att = 0.0, gate_rel = 0.0;
+  double room = 0.0, damp = 0.0, wet = 0.0, dry = 0.0, width = 0.0;
+  double lo_db = 0.0, hi_db = 0.0, lo_fc = 440.0, hi_fc = 440.0, lo_q = M_SQRT1_2, hi_q = M_SQRT1_2;
+  double rate = 0.0, depth = 0.0, centre = 0.0, fb = 0.0, mix = 0.0;
+};
+// every refusal of a plan, before anything is written (api_fx.hip)
+void fx_validate(const char* who, const FxPlan& P);
+// the whole board from the eighteen add_effects values: validated with every stage on, identities switched off
+FxPlan fx_board_plan(const char* who, const rvcx_fx_params& p, int sr, int channels, bool low_rate);
+
+
 // A live-stream session (rvcx_stream_open): S lock-step streams of one geometry on one voice model.  Ring, carry and block
 // staging are allocations of the session's own (the arena is scratch that other calls reset).  Ring and carry exist twice: a
 // step reads set `cur` and writes the other one, and the sets change places once the step has succeeded -- the body of a step
@@ -91,7 +110,16 @@ struct StreamSession {
   // RVCX_STREAM_FULL_SYNTH=1 (read at open; tools/bench_stream.py's A/B): the synthesizer runs with skip_head = 0 and SOLA takes
   // the tail of the whole output -- what the step costs without the tail-only path (and NOT what the reference computes)
   bool full_synth = false;
+  // the effects board behind the output resampler (rvcx_stream_open_fx; rvcx.h "live post-production"): its state sets change
+  // places with everything else, its memory is the session's own
+  std::unique_ptr<FxLive> fx;
+  rvcx_fx_params fxp{};                    // the parameters in force
+  float* fx_out = nullptr;                 // (S, block, 2): what the step copies out
+  float fx_ms[8] = {0};                    // rvcx_stream_last_fx_ms
   ~StreamSession() {
+    if (fx)
+      for (void* q : {(void*)fx->state[0], (void*)fx->state[1], (void*)fx->work, (void*)fx_out})
+        if (q) (void)hipFree(q);
     for (void* q : {(void*)ring[0], (void*)ring[1], (void*)carry[0], (void*)carry[1], (void*)blocks[0], (void*)blocks[1],
                     (void*)stage, (void*)native[0], (void*)native[1], (void*)tables[0], (void*)tables[1], (void*)in.fifo[0],
                     (void*)in.fifo[1], (void*)out.fifo[0], (void*)out.fifo[1]})
@@ -206,6 +234,9 @@ int api_call(rvcx_ctx* ctxp, bool repeat, F&& body, bool drain = true) {
     return -1;
   }
 }
+
+// the session of an id, or a failure (api_stream.hip)
+StreamSession& get_session(rvcx_ctx* h, int id);
 
 // Tuning / fault-injection hooks (rvcx_conv_override, rvcx_debug_inject, rvcx_bench_*) are process-wide levers a serving
 // process must never meet by accident: they are refused (-2) unless the process was started with RVCX_DEBUG=1

@@ -1,8 +1,18 @@
-// C ABI of librvcx.so (include/rvcx.h): live-stream sessions.
+// C ABI of librvcx.so (include/rvcx.h): live-stream sessions (api_stream_fx.hip: the effects board inside them).
 #include "api_internal.h"
 
 using namespace rvcx;
 using namespace rvcx::api;
+
+namespace rvcx {
+namespace api {
+StreamSession& get_session(rvcx_ctx* h, int id) {
+  auto it = h->sessions.find(id);
+  if (it == h->sessions.end()) fail("stream: unknown session " + std::to_string(id));
+  return *it->second;
+}
+}  // namespace api
+}  // namespace rvcx
 
 extern "C" {
 
@@ -43,12 +53,6 @@ static size_t stream_step_bytes(Ctx& c, const SynthModel& M, const rvcx_params& 
   need += (size_t)S * ((size_t)Bout + 64) * 4;
   if (c.index) need += index_arena_bytes(*c.index, Th);
   return need + ((size_t)64 << 20);
-}
-
-static StreamSession& get_session(rvcx_ctx* h, int id) {
-  auto it = h->sessions.find(id);
-  if (it == h->sessions.end()) fail("stream: unknown session " + std::to_string(id));
-  return *it->second;
 }
 
 static const char kRateRule[] =
@@ -273,6 +277,11 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
       launch_stream_resample(se.out.g, se.out.f, se.out.fifo[se.cur], se.out.fifo[se.cur ^ 1], dout, Lb, r, Bout, S, se.step, st);
       dres = r, Lo = Bout;
     }
+    // (7) a session with effects: the board on what would have left, from the state it carries; stereo leaves
+    if (se.fx) {
+      fx_live_step(*se.fx, dres, Lo, 1, se.cur, se.step, se.fx_out, 2 * Lo, st, ev + 8);
+      dres = se.fx_out, Lo *= 2;
+    }
     for (int s = 0; s < S; ++s) {
       RVCX_HIP(hipMemcpyAsync(out[s], dres + (size_t)s * Lo, (size_t)Lo * 4, hipMemcpyDefault, st));
       if (pre_sola) RVCX_HIP(hipMemcpyAsync(pre_sola[s], tail + (size_t)s * Lsyn, (size_t)Lk * 4, hipMemcpyDefault, st));
@@ -287,6 +296,10 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
       ms[0] = 0.f;
       for (int k = 1; k <= 7; ++k) RVCX_HIP(hipEventElapsedTime(&ms[k], ev[k - 1], ev[k]));
       RVCX_HIP(hipEventElapsedTime(&ms[8], ev[0], ev[7]));
+      if (se.fx) {
+        for (int k = 0; k < 7; ++k) RVCX_HIP(hipEventElapsedTime(&se.fx_ms[k], ev[8 + k], ev[9 + k]));
+        RVCX_HIP(hipEventElapsedTime(&se.fx_ms[7], ev[8], ev[15]));
+      }
     }
     A.reset();
     done = &se;
@@ -307,6 +320,8 @@ int rvcx_stream_reset(rvcx_ctx* ctx, int stream_id) {
   if (se.native[se.cur]) RVCX_HIP(hipMemsetAsync(se.native[se.cur], 0, (size_t)se.S * se.Lb * 4, C->stream));
   for (StreamSide* sd : {&se.in, &se.out})
     if (sd->fifo[se.cur]) RVCX_HIP(hipMemsetAsync(sd->fifo[se.cur], 0, (size_t)se.S * sd->g.L * sizeof(double), C->stream));
+  if (se.fx)        // a ring of the board is complete only over both sets
+    for (float* q : se.fx->state) RVCX_HIP(hipMemsetAsync(q, 0, (size_t)se.S * se.fx->L.per_stream * 4, C->stream));
   RVCX_HIP(hipStreamSynchronize(C->stream));
   se.step = 0;
   API_END

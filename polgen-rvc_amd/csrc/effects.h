@@ -1,5 +1,6 @@
 // Post-production (include/rvcx.h "post-production"): the vocal effects chain and the cover mix.  effects.hip holds the
-// kernels, their launchers, the coefficient formulas and the sequential host twins; api_fx.hip the entry points.
+// kernels, their launchers, the coefficient formulas and the sequential host twins; api_fx.hip the entry points;
+// effects_live.hip the board of a live session (state carried across blocks); effects_device.h the step functions all share.
 //
 // Device layout: planar rows.  Row r = item * C + channel holds len[r] samples at the front of ld floats (ld a multiple of
 // kFxChunk, the tail zero).  Every kernel takes one row per blockIdx.y and cuts it into chunks counted from the row's first
@@ -66,5 +67,52 @@ void fx_comb_host(const float* in, long n, int D, float fb, float d, float* out)
 void fx_allpass_host(const float* in, long n, int D, float* out);
 void fx_chorus_host(const FxChorus& ch, const float* x, long n, float* y);
 void fx_mix_host(const int16_t* v, long nv, const int16_t* inst, long ni, double gv, double gi, int16_t* out);
+// the whole reverb on one stereo item, x and y (n, 2) interleaved: fx_comb_host / fx_allpass_host and the mix FMAs
+void fx_reverb_host(const FxReverb& rv, const float* x, long n, float* y);
+
+// ---- the board inside a live session (effects_live.hip; rvcx.h "live post-production") --------------------------------------
+// Every stage runs sequentially in sample order from state the session carries, so a step's output is the stage on the whole
+// signal whatever the cut.  State exists twice: a step reads one set and writes the other.
+inline bool fx_live_rate_ok(int sr, bool low) { return fx_rate_ok(sr) || (low && sr >= 3200 && sr < 8000 && sr % 100 == 0); }
+
+// what a step launches: on[k] says whether stage k + 1 runs; the rest is formed on the host in double and rounded once
+struct FxLivePlan {
+  bool on[7] = {false, false, false, false, false, false, false};
+  FxBiquad hp{}, lo{}, hi{};
+  float comp_ca = 0, comp_cr = 0, comp_thr = 1, comp_expo = 0;
+  float gate_c0 = 0, gate_c50 = 0, gate_ca = 0, gate_cr = 0, gate_thr = 1, gate_expo = 0;
+  FxReverb rv{};
+  FxChorus ch{};
+};
+
+// A stream's state, in floats from its start (fixed by rate and block, whatever the parameters): the scalar slots below, then
+// the delay lines (each indexed by the global sample index mod its length) and one chorus ring per channel.
+constexpr int kFxlBiquad = 0;      // stage j in {high-pass, low shelf, high shelf}, channel c: (s1, s2) at 4 j + 2 c
+constexpr int kFxlFollow = 12;     // compressor e at c, gate r at 2 + c, gate e at 4 + c
+constexpr int kFxlLast = 18;       // the combs' one-pole states at 8 side + comb
+constexpr int kFxlLines = 34;
+struct FxLiveLayout {
+  int comb[2][8], ap[2][4];        // (a side's all-pass lines follow each other)
+  long chorus[2];
+  long cap;                        // chorus ring: sr + 2 (the longest delay the board accepts, 1000 ms) + two blocks
+  long per_stream;
+};
+FxLiveLayout fx_live_layout(int sr, long block);
+
+struct FxLive {
+  int S = 0, sr = 0;
+  long B = 0;                      // samples per block and row
+  FxLiveLayout L{};
+  FxLivePlan plan;
+  float* state[2] = {nullptr, nullptr};   // (S, L.per_stream) each
+  float* work = nullptr;                  // fx_live_work_floats(S, B): two planes of 2 S rows and the 16 S comb rows
+};
+inline size_t fx_live_work_floats(int S, long B) { return (size_t)20 * S * B; }
+// One block of every stream through the stages that are on.  src: S rows of B frames of C interleaved floats, src_stride
+// floats apart; out: S rows of (B, 2), out_stride floats apart.  Reads state[cur], writes state[cur ^ 1]; step: blocks since
+// sample 0.  No host synchronisation.  ev (optional, 8 events): recorded in front of stage 1 and behind every stage -- the
+// load is counted with the high-pass, the interleave with the chorus.
+void fx_live_step(const FxLive& f, const float* src, long src_stride, int C, int cur, uint64_t step, float* out,
+                  long out_stride, hipStream_t s, hipEvent_t* ev);
 
 }  // namespace rvcx

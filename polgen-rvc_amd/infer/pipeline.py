@@ -371,7 +371,7 @@ class VC:
 
     def stream_open(self, model, net_g, sids, pitches, f0_method, file_index, index_rate, version, protect, *,
                     block_ms, context_ms, crossfade_ms, search_ms, f0_min=50, f0_max=1100, input_sr=16000,
-                    input_channels=1, output_sr=None):
+                    input_channels=1, output_sr=None, effects=None):
         """A live-stream session: len(sids) lock-step streams of one geometry on voice model ``net_g``.  Every
         ``session.step(blocks)`` takes one (S, block_ms * 16) float32 block of 16 kHz mono audio per stream and returns the
         converted (S, block_ms * tgt_sr / 1000) float32 blocks: rolling context, tail-only synthesis (Synthesizer.infer's
@@ -379,7 +379,15 @@ class VC:
         -- (S, frames, channels) for several channels -- and are brought to 16 kHz mono on the device; ``output_sr`` (None or
         tgt_sr: none): the blocks leave at that rate.  Both resamplers are stateful (``session.in_delay``, ``out_delay``,
         ``latency_ms``); rates are multiples of 100 Hz.  No high-pass, volume envelope, resample_sr or peak normalisation:
-        those are whole-clip operations of ``pipeline``.  Checks of version, method and index as in ``pipeline_batch``."""
+        those are whole-clip operations of ``pipeline``.  ``effects``: a dict of ``add_effects`` names laid over the processing
+        tab's defaults (or an ``FxParams``) -- the effects board then runs inside every step, with its state carried from
+        block to block, and ``step`` returns stereo (S, frames, 2); ``session.set_effects(**changes)`` changes values live.
+        Checks of version, method and index as in ``pipeline_batch``."""
+        if effects is not None:
+            try:
+                effects = _lib.fx_values(effects)            # unknown names are refused before any work
+            except _lib.RvcxError as e:
+                raise ValueError(str(e)) from None
         for name, v in (("input_sr", input_sr), ("output_sr", output_sr)):
             if v is not None and (int(v) != v or int(v) <= 0 or int(v) % 100 != 0):
                 raise ValueError(f"{name}={v!r}: a multiple of 100 Hz (a 10 ms frame is a whole number of samples)")
@@ -403,7 +411,8 @@ class VC:
         p = self._params(0.0, index_rate if index is not None else 0.0, 1.0, protect, f0_min, f0_max, sids[0],
                          f0_method=f0_method)
         return ctx.stream_open(net_g.model_id, p, sids, pitches, Fb, Fc, Fx, Fs, in_rate=int(input_sr),
-                               in_channels=int(input_channels), out_rate=0 if output_sr is None else int(output_sr))
+                               in_channels=int(input_channels), out_rate=0 if output_sr is None else int(output_sr),
+                               effects=effects)
 
     def pipeline_async(self, model, net_g, sid, audio, input_audio_path, pitch, f0_method, file_index, index_rate,
                        pitch_guidance, filter_radius, tgt_sr, resample_sr, volume_envelope, version, protect,

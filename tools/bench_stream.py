@@ -8,7 +8,10 @@ p99 per run, and the per-stage device times of rvcx_last_timing.  Then the same 
 With `--in-rate` / `--in-channels` / `--out-rate` every S is measured a second time as a rate session (rvcx_stream_open_io:
 the blocks arrive at the sound card's rate and leave at `--out-rate`), on the same model and the same audio, so the step with
 and without the two resamplers stands side by side; the result gains the delays and the difference.  `--model 40k` measures
-on the 40 k voice model (48 kHz out of it is a real conversion; out of the 48 k model it is none).
+on the 40 k voice model (48 kHz out of it is a real conversion; out of the 48 k model it is none).  A rate session is then
+measured a third and fourth time with the effects board inside the step (rvcx_stream_open_fx): at the processing tab's defaults,
+and with the chorus and both shelves on; the result gains the board's cost beside the rate session without it and the per-stage
+device times of rvcx_stream_last_fx_ms.  `--no-effects` leaves these out.
 
 The one criterion that can be derived is real time itself: a step must take less than the block it converts.  The result
 records, per S, whether the median and the p99 do, and the largest S whose p99 does.  Not part of bench.py.
@@ -32,6 +35,9 @@ from polgen_rvc_amd import _lib, synthetic as S  # noqa: E402
 
 BLOCK_MS, CONTEXT_MS, CROSSFADE_MS, SEARCH_MS = 100, 2500, 50, 10
 STAGES = ["f0", "hubert", "blend_mix", "enc_p", "flow", "decoder", "sola_copies", "total"]
+FX_CASES = {"ui_defaults": {},
+            "chorus_and_shelves": dict(low_shelf_gain=3.0, high_shelf_gain=-2.0, chorus_rate_hz=1.5, chorus_depth=0.25,
+                                       chorus_centre_delay_ms=7.0, chorus_feedback=0.3, chorus_mix=0.5)}
 
 
 def mic_blocks(clips, in_rate, in_channels):
@@ -45,7 +51,7 @@ def mic_blocks(clips, in_rate, in_channels):
     return x if in_channels == 1 else np.ascontiguousarray(np.repeat(x[:, :, None], in_channels, axis=2))
 
 
-def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None):
+def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effects=None):
     os.environ["RVCX_STREAM_FULL_SYNTH"] = "1" if full_synth else "0"      # read when the session opens
     p = bench.make_params(seed=1)
     io = io or {}
@@ -53,8 +59,9 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None):
     need = (warmup + steps) * Fb * 160
     clips = np.stack([S.make_clip(100 + s, need / 16000.0 + 0.1)[:need] for s in range(n_streams)]).astype(np.float32)
     clips = mic_blocks(clips, io.get("in_rate", 0), io.get("in_channels", 1))
-    runs, stage_ms = [], []
-    with ctx.stream_open(mid, p, [0] * n_streams, [float(s % 5 - 2) for s in range(n_streams)], Fb, Fc, Fx, Fs, **io) as se:
+    runs, stage_ms, fx_ms = [], [], []
+    with ctx.stream_open(mid, p, [0] * n_streams, [float(s % 5 - 2) for s in range(n_streams)], Fb, Fc, Fx, Fs, effects=effects,
+                         **io) as se:
         geo = dict(ring_frames=Fc + Fx + Fs + Fb, frames=se.frames, skip_head=se.skip_head, block_in=se.block_in,
                    block_out=se.block_out, in_delay=se.in_delay, out_delay=se.out_delay, latency_ms=round(se.latency_ms, 3))
         for r in range(repeats):
@@ -69,15 +76,22 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None):
                     ms.append(1e3 * dt)
                     tm = ctx.last_timing()
                     stage_ms.append([tm[n] for n in ("rmvpe", "hubert", "index", "enc_p", "flow", "decoder", "post", "total")])
+                    if effects is not None:
+                        fx_ms.append(list(se.last_fx_ms().values()))
             assert np.isfinite(out).all() and out.any()
             ms = np.asarray(ms)
             runs.append(dict(median_ms=round(float(np.median(ms)), 3), p99_ms=round(float(np.percentile(ms, 99)), 3),
                              max_ms=round(float(ms.max()), 3)))
-            print(f"  S={n_streams} full_synth={int(full_synth)} io={io} run {r}: {runs[-1]}", flush=True)
+            print(f"  S={n_streams} full_synth={int(full_synth)} io={io} effects={effects is not None} run {r}: {runs[-1]}",
+                  flush=True)
     st = np.median(np.asarray(stage_ms), axis=0)
-    return dict(geometry=geo, runs=runs, median_ms=round(float(np.median([r["median_ms"] for r in runs])), 3),
-                p99_ms=round(float(np.max([r["p99_ms"] for r in runs])), 3),
-                stage_ms_median={n: round(float(v), 3) for n, v in zip(STAGES, st)})
+    res = dict(geometry=geo, runs=runs, median_ms=round(float(np.median([r["median_ms"] for r in runs])), 3),
+               p99_ms=round(float(np.max([r["p99_ms"] for r in runs])), 3),
+               stage_ms_median={n: round(float(v), 3) for n, v in zip(STAGES, st)})
+    if effects is not None:
+        names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "total"]
+        res["fx_ms_median"] = {n: round(float(v), 4) for n, v in zip(names, np.median(np.asarray(fx_ms), axis=0))}
+    return res
 
 
 def main():
@@ -91,6 +105,7 @@ def main():
     ap.add_argument("--in-rate", type=int, default=0, help="Hz of the blocks a rate session takes (0: 16 kHz)")
     ap.add_argument("--in-channels", type=int, default=1)
     ap.add_argument("--out-rate", type=int, default=0, help="Hz of the blocks a rate session returns (0: the model's rate)")
+    ap.add_argument("--no-effects", action="store_true", help="skip the rate session with the effects board inside the step")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_stream.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -118,6 +133,16 @@ def main():
                               stage_ms_median=q["stage_ms_median"], real_time_p99=bool(q["p99_ms"] < BLOCK_MS),
                               resampling_costs_ms=round(q["median_ms"] - r["median_ms"], 3),
                               resampling_costs_device_ms=round(q["stage_ms_median"]["total"] - r["stage_ms_median"]["total"], 3))
+            if not a.no_effects:      # and with the board behind the output resampler, in the same process
+                r["effects"] = {}
+                for name, fx in FX_CASES.items():
+                    e = run(ctx, mid, n_streams, a.steps, a.warmup, a.repeats, False, io, effects=fx)
+                    r["effects"][name] = dict(values=fx, runs=e["runs"], median_ms=e["median_ms"], p99_ms=e["p99_ms"],
+                                              stage_ms_median=e["stage_ms_median"], fx_ms_median=e["fx_ms_median"],
+                                              real_time_p99=bool(e["p99_ms"] < BLOCK_MS),
+                                              board_costs_ms=round(e["median_ms"] - q["median_ms"], 3),
+                                              board_costs_device_ms=round(e["stage_ms_median"]["total"]
+                                                                          - q["stage_ms_median"]["total"], 3))
         res["streams"][str(n_streams)] = r
     ok = [int(k) for k, v in res["streams"].items() if v["real_time_p99"]]
     res["largest_streams_real_time_p99"] = max(ok) if ok else 0

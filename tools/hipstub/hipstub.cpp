@@ -129,6 +129,10 @@ hipError_t hipMemset(void* d, int v, size_t n) {
   return hipSuccess;
 }
 hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t) { return hipMemset(d, v, n); }
+hipError_t hipMemset2DAsync(void* d, size_t pitch, int v, size_t w, size_t h, hipStream_t) {
+  for (size_t r = 0; r < h; ++r) memset((char*)d + r * pitch, v, w);
+  return hipSuccess;
+}
 
 hipError_t hipHostFree(void* p) { return hipFree(p); }
 hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) {
