@@ -695,6 +695,45 @@ int rvcx_gru_publish_probe(rvcx_ctx*);
 /* retrieval: queries whose 8 neighbours could not be certified from the split-fp16 pre-filter and were searched
  * exhaustively instead (csrc/index.hip) since the last call of this function; waits for the device.  -1: no index */
 int64_t rvcx_index_exhaustive(rvcx_ctx*);
+
+/* ---- index building ("train index" of the RVC UIs; csrc/kmeans.hip) --------------------------------------------------------
+ * The reference ships no index trainer: the UIs call faiss (IVF{n},Flat trained on the stacked HuBERT features) and, above
+ * 200 000 rows, scikit-learn's MiniBatchKMeans first.  Neither is restated here (parity with their clustering is unpinned);
+ * the stages are DEFINED below and checked against a float64 restatement (tests/kmeans_reference.py).
+ *
+ * rvcx_kmeans: `iters` >= 1 Lloyd iterations on x (n, dim) from C_0 = init (k, dim).  Iteration i:
+ *  - assign.  a_i[r] = the centroid c with the smallest EXACT fp32 pair distance e(x, c) = |c|^2 - 2 dot(x, c); ties go to
+ *    the smaller id.  One fp32 routine computes e for a pair, whatever path reached the pair (kmeans.hip: pair_dot; its
+ *    error is below 2^-18 (|x||c| + |c|^2)).  The split-fp16 GEMM pre-filters: the pick of a row is used only when it is
+ *    certified against the filter's error bound; other rows -- and rows or centroids with values beyond fp16 range -- are
+ *    scanned over all k centroids.  The result does not depend on the filter, the tiling or the row chunks:
+ *    RVCX_KMEANS_PREFILTER=0 (read once per process; every row takes the scan) gives the same bits.
+ *  - objective[i] = sum_r (|x_r|^2 + e(x_r, C_i[a_i[r]])), |x|^2 and the sum in double in a fixed order.
+ *  - update.  C_{i+1}[c] = the mean of c's members, added in double in ascending row order, rounded once to float32; no
+ *    floating-point atomics, the same bits in every run.  A cluster without members keeps its centroid for the next step.
+ *  - empty clusters, after the update, in ascending id: an empty c takes the centroid of the cluster j that is largest by the
+ *    running counts (ties: smaller id); float32 products: c's even dimensions x (1 + 2^-10), odd x (1 - 2^-10), j's the other
+ *    way round; for the remaining empties c then counts count[j] / 2 (integer division) and j the rest.  splits[i] = the
+ *    number of clusters treated.
+ * Outputs: centroids = C_iters (k, dim); assign = a_{iters-1} (n); counts = the histogram of assign (k), before any split
+ * bookkeeping; objective, splits: `iters` values each in HOST memory.  Every output pointer may be NULL.
+ * Refused: k > n, k < 1, iters < 1, dim % 16 != 0, dim > 1024 (the limit of csrc/index.hip), n >= 2^31. */
+int rvcx_kmeans(rvcx_ctx*, const float* x_hd, int64_t n, int dim, const float* init_hd, int k, int iters,
+                float* centroids_hd, int32_t* assign_hd, int32_t* counts_hd, double* objective, int32_t* splits);
+/* the inverted list of every stored row of an IVF{nlist},Flat index: the search's own coarse quantiser (rvcx_index_blend on an
+ * IVF index: nearest centroid by |q|^2 + |c|^2 - 2 q.c on exact-fp32 dots, the first minimum on ties), so a stored vector
+ * used as a query probes the list it was filed under -- outside fp32 rounding of the coarse distance: the fp32 dots of a chunk
+ * of thousands of rows and of a few queries may be summed in another order (tile and split-K follow the row count), so two
+ * centroids closer than that rounding can change places.  Refused: dim > 1024, nlist < 1, n < 1 */
+int rvcx_ivf_assign(rvcx_ctx*, const float* x_hd, int64_t n, int dim, const float* centroids_hd, int nlist,
+                    int32_t* assign_hd);
+/* the rows an index is built from: what VC.vc hands the retrieval blend (pipeline.py:228-236) for B clips of n samples --
+ * out_dim = the HuBERT's embed_dim: the output of layer 12 (RVC v2); out_dim = its final_proj width: final_proj of the
+ * output of layer 9 (RVC v1).  feats (B, rvcx_hubert_frames(n), out_dim) */
+int rvcx_index_features(rvcx_ctx*, int B, const float* wav_hd, int64_t n, int out_dim, float* feats_hd);
+/* rows of the last rvcx_kmeans call (summed over its iterations) that took the exact scan; -1 without a context */
+int64_t rvcx_kmeans_exhaustive(rvcx_ctx*);
+
 /* DEBUG HOOKS -- rvcx_debug_inject, rvcx_bench_resblock_pair, rvcx_bench_conv1d, rvcx_bench_gemm, rvcx_conv_override are
  * process-wide tuning / fault-injection levers.  They return -2 ("refused") unless the process was started with
  * RVCX_DEBUG=1 in its environment (read once); the product path never calls them. */

@@ -172,6 +172,7 @@ SYMBOLS = [
     "rvcx_fx_gate_host", "rvcx_fx_comb_host", "rvcx_fx_allpass_host", "rvcx_fx_chorus_host", "rvcx_fx_mix_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
+    "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
     "rvcx_op_resblock3", "rvcx_flac_encode_bound", "rvcx_flac_encode_s16", "rvcx_flac_info", "rvcx_flac_decode_s32", "rvcx_flac_last_error",
 ]
 
@@ -199,6 +200,10 @@ def lib() -> C.CDLL:
         _lib.rvcx_noise_len.restype = C.c_int64
         _lib.rvcx_crepe_frames.restype = C.c_int64
         _lib.rvcx_index_exhaustive.restype = C.c_int64
+        _lib.rvcx_kmeans_exhaustive.restype = C.c_int64
+        _lib.rvcx_kmeans.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.rvcx_ivf_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         _lib.rvcx_flac_encode_bound.restype = C.c_int64
         _lib.rvcx_flac_encode_s16.restype = C.c_int64
         _lib.rvcx_flac_decode_s32.restype = C.c_int64
@@ -1279,6 +1284,46 @@ class Context:
         self._ck(lib().rvcx_index_blend(self._h, _p(f), T, C.c_float(index_rate), _p(ids, C.c_int64), _p(dist)),
                  "index_blend")
         return f, ids, dist
+
+    # ---- index building (rvcx.h "index building"; index_build.py is the product-side caller) ----
+    def kmeans(self, x, init, iters=1):
+        """`iters` Lloyd iterations from the centroids `init` -> dict(centroids (k, dim), assign (n) of the LAST assignment
+        step, counts (k) = its histogram, objective (iters) float64, splits (iters) empty clusters treated per iteration)."""
+        x, init = f32(x), f32(init)
+        if x.ndim != 2 or init.ndim != 2 or x.shape[1] != init.shape[1]:
+            raise ValueError("kmeans: x (n, dim) and init (k, dim) must be matrices of one width")
+        (n, dim), k, iters = x.shape, init.shape[0], int(iters)
+        cent = np.empty((k, dim), np.float32)
+        assign, counts = np.empty(n, np.int32), np.empty(k, np.int32)
+        obj, splits = np.zeros(max(iters, 1), np.float64), np.zeros(max(iters, 1), np.int32)
+        self._ck(lib().rvcx_kmeans(self._h, x.ctypes.data, n, dim, init.ctypes.data, k, iters, cent.ctypes.data,
+                                   assign.ctypes.data, counts.ctypes.data, obj.ctypes.data, splits.ctypes.data), "kmeans")
+        return dict(centroids=cent, assign=assign, counts=counts, objective=obj, splits=splits)
+
+    def ivf_assign(self, x, centroids):
+        """list id (int32) of every row: the coarse quantiser of the IVF search, the first minimum on ties"""
+        x, c = f32(x), f32(centroids)
+        if x.ndim != 2 or c.ndim != 2 or x.shape[1] != c.shape[1]:
+            raise ValueError("ivf_assign: x (n, dim) and centroids (nlist, dim) must be matrices of one width")
+        a = np.empty(x.shape[0], np.int32)
+        self._ck(lib().rvcx_ivf_assign(self._h, x.ctypes.data, x.shape[0], x.shape[1], c.ctypes.data, c.shape[0],
+                                       a.ctypes.data), "ivf_assign")
+        return a
+
+    def index_features(self, wav, out_dim):
+        """the rows an index is built from, (B, T, out_dim): HuBERT layer 12 (out_dim = embed_dim, RVC v2) or final_proj of
+        layer 9 (out_dim = its width, RVC v1) -- what VC.vc hands the retrieval blend"""
+        wav = f32(wav)
+        if wav.ndim == 1:
+            wav = wav[None]
+        B, n = wav.shape
+        out = np.empty((B, self.hubert_frames(n), int(out_dim)), np.float32)
+        self._ck(lib().rvcx_index_features(self._h, B, _p(wav), C.c_int64(n), int(out_dim), _p(out)), "index_features")
+        return out
+
+    def kmeans_exhaustive(self) -> int:
+        """rows of the last kmeans() call (over all its iterations) that took the exact scan over every centroid"""
+        return int(lib().rvcx_kmeans_exhaustive(self._h))
 
     def highpass(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)

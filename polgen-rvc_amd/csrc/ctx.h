@@ -218,6 +218,7 @@ struct Ctx {
   long fp32_reruns = 0;           // calls repeated because of that (each repeat pins one layer to fp32, or, last resort, all)
   long gru_fallbacks = 0;         // calls repeated with the single-workgroup BiGRU kernel after a cluster time-out
   bool inject_gru_timeout = false;
+  int64_t kmeans_exhaustive = 0;  // rows of the last rvcx_kmeans call that took the exact scan over all centroids (kmeans.hip)
   // ---- conversion tickets (rvcx_convert_submit, api_convert.hip): at most two in flight, each in a slot of its own.  A slot owns
   // what a ticket needs for its whole life (PCM, float waveform, parity noise, f0-file track, both front sets), a device
   // error word with its pinned host copy (dev_err points at the word of the ticket being enqueued, at words[0] otherwise: an

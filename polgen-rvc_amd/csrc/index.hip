@@ -440,4 +440,31 @@ void index_blend(Ctx& c, const IndexData& ix, float* feats_ct, int T, float inde
   RVCX_HIP(hipGetLastError());
 }
 
+// ---- the coarse quantiser on its own: what index building (kmeans.hip) files the stored rows with.  The same kernels on
+// the same exact-fp32 dots as the search above, so a stored vector used as a query probes the list it was filed under.
+std::vector<float> index_sq_norms(const float* m, int64_t rows, int dim) {
+  std::vector<float> out((size_t)rows);
+  for (int64_t i = 0; i < rows; ++i) {
+    float s = 0.f;
+    for (int d = 0; d < dim; ++d) s += m[i * dim + d] * m[i * dim + d];
+    out[(size_t)i] = s;
+  }
+  return out;
+}
+
+size_t index_coarse_arena_bytes(int nlist, int T) { return ((size_t)nlist * T + 2 * (size_t)T) * sizeof(float) + 4096; }
+
+void index_coarse_assign(Ctx& c, const ConvW& cent, const float* cent_norms, const float* feats_ct, int T, int* qlist,
+                         hipStream_t s) {
+  RVCX_CHECK(cent.cin <= kMaxDim, "index: feature dimension above 1024");
+  Arena& A = c.arena;
+  float* qn = A.alloc<float>((size_t)T);
+  hipLaunchKernelGGL(qnorm_kernel, dim3(cdiv(T, 64)), dim3(1024), 0, s, feats_ct, qn, cent.cin, T);
+  float* cdots = A.alloc<float>((size_t)cent.cout * T);
+  ConvArgs a = conv1d_args(cent, feats_ct, cdots, 1, T, T);
+  c.conv_on(a, s);
+  hipLaunchKernelGGL(coarse_assign_kernel, dim3(cdiv(T, 256)), dim3(256), 0, s, cdots, cent_norms, qn, qlist, cent.cout, T);
+  RVCX_HIP(hipGetLastError());
+}
+
 }  // namespace rvcx

@@ -232,6 +232,23 @@ size_t index_arena_bytes(const IndexData& ix, int T);
 // feats_ct (dim, T) channel-first in/out (device); ids (T,8) int64 / dist (T,8) optional device outputs
 void index_blend(Ctx& c, const IndexData& ix, float* feats_ct, int T, float index_rate, int64_t* ids,
                  float* dist, hipStream_t s);
+// the search's coarse quantiser without an index (index.hip): list id per query, the first minimum on ties.  cent: the
+// (nlist, dim) centroids packed WITHOUT a split image (exact-fp32 dots), cent_norms = index_sq_norms of them on the device.
+// Takes index_coarse_arena_bytes from the arena.
+std::vector<float> index_sq_norms(const float* m, int64_t rows, int dim);
+size_t index_coarse_arena_bytes(int nlist, int T);
+void index_coarse_assign(Ctx& c, const ConvW& cent, const float* cent_norms, const float* feats_ct, int T, int* qlist,
+                         hipStream_t s);
+
+// ------------------------------------------------------------------------------ index building (kmeans.hip; rvcx.h)
+struct KmeansResult {
+  int64_t exhaustive = 0;       // rows (summed over the iterations) that took the exact scan over all centroids
+};
+// x (n, dim), init (k, dim): host or device.  centroids (k, dim), assign (n), counts (k): host or device, may be null.
+// objective / splits: host, `iters` values each, may be null.
+KmeansResult kmeans_run(Ctx& c, const float* x, int64_t n, int dim, const float* init, int k, int iters, float* centroids,
+                        int32_t* assign, int32_t* counts, double* objective, int32_t* splits);
+void ivf_assign_run(Ctx& c, const float* x, int64_t n, int dim, const float* centroids, int nlist, int32_t* assign);
 
 // ------------------------------------------------------------------------------ host helpers
 // weight-norm fold  w = g * v / ||v||  over all dims except `dim` (0 or 2)

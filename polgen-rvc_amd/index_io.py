@@ -1,6 +1,8 @@
 """``.index`` files -> the (N, dim) float32 matrix ``index.reconstruct_n(0, ntotal)`` returns
 (rvc/infer/pipeline.py:322-323), without faiss.
 
+``write_index`` is the inverse: the product-side writer of the two layouts (index_build.py).
+
 Supported: ``.npy`` dumps of big_npy, FAISS ``IndexFlat`` ("IxF2"/"IxFI") and ``IndexIVFFlat`` ("IwFl",
 array inverted lists).  The FAISS binary layouts are restated from the published faiss 1.7 io format
 (impl/index_read.cpp: read_index_header, read_ivf_header, read_direct_map, read_InvertedLists); faiss is not
@@ -129,3 +131,61 @@ def read_index(path: str) -> IndexFile:
 
 def read_index_vectors(path: str) -> np.ndarray:
     return read_index(path).vectors
+
+
+# ---- writing (faiss/impl/index_write.cpp: write_index_header, write_ivf_header, write_direct_map, write_InvertedLists)
+def _w_header(d, ntotal):
+    # d, ntotal, two unused words (faiss writes 1 << 20), is_trained, METRIC_L2
+    return struct.pack("<iqqqBi", d, ntotal, 1 << 20, 1 << 20, 1, 1)
+
+
+def _w_vec(a, dtype):
+    a = np.ascontiguousarray(a, dtype)
+    return struct.pack("<Q", a.size) + a.tobytes()
+
+
+def _w_flat(v):
+    return b"IxF2" + _w_header(v.shape[1], v.shape[0]) + _w_vec(v.ravel(), np.float32)
+
+
+def index_bytes(vectors, centroids=None, assign=None, nprobe=1) -> bytes:
+    """The file ``write_index`` writes.  Flat ("IxF2") without centroids; otherwise "IwFl" with array inverted lists,
+    ``full`` sizes, no direct map, ids = row numbers in ascending order inside a list (what ``index.add(big_npy)`` on a
+    trained faiss index leaves)."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2:
+        raise ValueError("write_index: vectors must be (n, dim)")
+    if centroids is None:
+        if assign is not None:
+            raise ValueError("write_index: list ids without centroids")
+        return _w_flat(v)
+    c = np.ascontiguousarray(centroids, np.float32)
+    if assign is None:
+        raise ValueError("write_index: an IVF index needs the list id of every vector")
+    a = np.asarray(assign)
+    n, d = v.shape
+    nlist = c.shape[0]
+    if c.ndim != 2 or c.shape[1] != d or a.shape != (n,):
+        raise ValueError("write_index: centroids must be (nlist, dim) and assign (n,)")
+    if n and (a.min() < 0 or a.max() >= nlist):
+        raise ValueError("write_index: list id out of range")
+    order = np.argsort(a, kind="stable").astype(np.int64)          # rows grouped by list, ascending inside a list
+    sizes = np.bincount(a, minlength=nlist).astype(np.uint64)
+    out = [b"IwFl", _w_header(d, n), struct.pack("<QQ", nlist, int(nprobe)), _w_flat(c),
+           struct.pack("<B", 0), struct.pack("<Q", 0),             # direct map: NoMap, empty array
+           b"ilar", struct.pack("<QQ", nlist, 4 * d), b"full", _w_vec(sizes, np.uint64)]
+    o = 0
+    for sz in sizes:
+        ids = order[o:o + int(sz)]
+        o += int(sz)
+        if len(ids):
+            out.append(v[ids].tobytes())
+            out.append(ids.tobytes())
+    return b"".join(out)
+
+
+def write_index(path: str, vectors, centroids=None, assign=None, nprobe=1) -> None:
+    """Inverse of ``read_index`` for FAISS files: ``read_index(path)`` returns these vectors, centroids, list ids, nprobe."""
+    data = index_bytes(vectors, centroids, assign, nprobe)
+    with open(path, "wb") as f:
+        f.write(data)
