@@ -210,18 +210,46 @@ def test_every_3x3_tile_stores_every_subtile(ctx, tile):
 
 @pytest.mark.parametrize("C,K,d,T", [(32, 3, 1, 5000), (32, 11, 5, 777), (64, 7, 3, 4099), (64, 11, 5, 300),
                                      (128, 3, 1, 1000), (128, 7, 1, 2500), (128, 11, 5, 1531), (128, 11, 3, 100),
-                                     (256, 3, 1, 700), (256, 3, 1, 1201)])
+                                     (256, 3, 1, 700), (256, 3, 1, 1201),
+                                     # persistent rows (T a multiple of 4), just over two tiles
+                                     (32, 7, 3, 1100), (32, 11, 1, 1100), (64, 3, 5, 600), (64, 7, 1, 600),
+                                     # dword rows (T odd), just over two tiles
+                                     (32, 3, 3, 1101), (32, 7, 5, 1101), (64, 3, 1, 601), (64, 11, 3, 601),
+                                     (128, 3, 5, 451), (128, 7, 3, 451)])
 def test_fused_resblock_pair_equals_two_launches(ctx, C, K, d, T):
     """One ResBlock1 step (residuals.py:45-53) as one kernel (resblock.hip): against torch fp32 within fp32
     rounding, and bit-identical to the two conv_h3 launches it replaces -- ragged batch (per-item lengths,
-    one of them shorter than a tile) included; every output element is written (NaN-filled destination)."""
+    one of them shorter than a tile) included; every output element is written (NaN-filled destination).
+
+    ctx.resblock_pair passes rows of T floats (cs = T), so the parity of T alone selects the form: T a multiple of 4 runs
+    the persistent kernel (C <= 128) or the per-tile kernel with the wide epilogue (C = 256), any other T the per-tile
+    kernel with the dword epilogue.  The cases launch each of the 20 instantiations of resblock.hip once."""
+    _fused_pair_case(ctx, C, K, d, T, np.array([T, max(1, T // 2 + 3), min(T, 17)], np.int32))
+
+
+# N1 of the persistent rows of resblock.hip (positions of the c1 tile); a tile stores (N1 - (k - 1)) & ~3 output positions
+PERSIST_N1 = {32: 512, 64: 256, 128: 192}
+
+
+@pytest.mark.parametrize("C,K,d", [(32, 3, 1), (64, 7, 3), (128, 11, 5)])
+def test_fused_resblock_persistent_workgroups_walk_several_tiles(ctx, C, K, d):
+    """The persistent kernel launches at most one workgroup per CU; here T = (2 CUs + 37) tiles, so every workgroup walks two
+    or three tiles (the cross-tile prefetch of input, weights and residual), and the split of tiles over XCDs and of an
+    XCD's tiles over its workgroups both leave remainders.  Same assertions as the test above."""
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    bn_out = (PERSIST_N1[C] - (K - 1)) & ~3
+    T = (2 * cus + 37) * bn_out
+    assert T % 4 == 0 and -(-T // bn_out) > 2 * cus
+    _fused_pair_case(ctx, C, K, d, T, np.array([T, T // 2 + 3], np.int32))
+
+
+def _fused_pair_case(ctx, C, K, d, T, lens):
     g = torch.Generator().manual_seed(C * 100 + K)
-    B = 3
+    B = len(lens)
     x = torch.randn(B, C, T, generator=g)
     w1 = torch.randn(C, C, K, generator=g) / (C * K) ** 0.5
     w2 = torch.randn(C, C, K, generator=g) / (C * K) ** 0.5
     b1, b2 = torch.randn(C, generator=g), torch.randn(C, generator=g)
-    lens = np.array([T, max(1, T // 2 + 3), min(T, 17)], np.int32)
     xm = x.clone()
     for b in range(B):
         xm[b, :, lens[b]:] = 0

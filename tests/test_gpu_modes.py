@@ -1,15 +1,19 @@
 """The non-default arithmetic modes, end to end against the REFERENCE goldens.
 
-The library chooses its kernels from environment variables read once per process, so each mode runs the golden tests of
-tests/test_gpu_pipeline.py in a fresh child process (started as a child, never an exec of this GPU-initialised one):
+The library chooses its kernels from environment variables read once per process, so each mode runs its tests in a fresh
+child process (started as a child, never an exec of this GPU-initialised one).  The arithmetic modes run the golden tests
+of tests/test_gpu_pipeline.py:
 
   RVCX_H3=0 RVCX_ATT_H3=0   every product on the exact-fp32 MFMA (v_mfma_f32_32x32x2_f32): the mode bench.py reports
                             as `exact_fp32`, and the mode an fp16-range overflow falls back to
   RVCX_FUSE=0               the NSF ResBlock steps as two conv launches instead of the fused kernel
   RVCX_GEMM=0               Linear layers on the channel-first conv tiles instead of the time-major GEMM kernel
 
-Each child runs: the multi-chunk tiny golden, the CI-argument tiny golden, C2 at full size (30 s, 48 k) and the
-float-waveform-vs-oracle test -- the same assertions as the default mode (float <= 1e-4 RMS, PCM <= 8 LSB)."""
+Each of these children runs: the multi-chunk tiny golden, the CI-argument tiny golden, C2 at full size (30 s, 48 k) and the
+float-waveform-vs-oracle test -- the same assertions as the default mode (float <= 1e-4 RMS, PCM <= 8 LSB).
+
+The dispatch modes below them (RVCX_PAIR_XCD, RVCX_GRU_*, RVCX_NO_SPLIT, RVCX_CONV_WS, RVCX_GEMM_BD, RVCX_DEC_BATCH,
+RVCX_RESBLOCK_STREAMS, RVCX_DEC_WINDOW, RVCX_HUBERT_FUSE0) run the kernel-level or golden tests named in their docstrings."""
 import os
 import subprocess
 import sys
@@ -46,19 +50,11 @@ def test_channel_first_linear_mode_passes_the_reference_goldens():
     _run_mode({"RVCX_GEMM": "0"})
 
 
-@pytest.mark.parametrize("variant", ["1", "2", "5", "6", "7", "8", "11", "13"])
-def test_alternative_fused_resblock_tiles_are_bit_identical_too(variant):
-    """RVCX_PAIR_VARIANT selects other forms of the fused ResBlock step (2: small tiles, two workgroups per CU; 5: 8 waves
-    of 64 x 64 on 256-position tiles with the input tile overlaid on Y1; 6 / 7: weights straight from L2 into registers,
-    barrier-free c2 loop; 8: split-phase staging on LDS counters, no s_barrier in the k-loops -- round-4 experiments; 11 / 13: round 5's persistent form with EARLY requests / the 512-thread N1 = 192 tile at k = 3): the k-order is the same, so each must equal the two conv
-    launches bit for bit and torch within fp32 rounding."""
-    _run_mode({"RVCX_PAIR_VARIANT": variant}, "test_gpu_conv.py", "fused_resblock", "10 passed")
-
-
-def test_per_tile_fused_step_of_round_4_is_bit_identical_too():
-    """RVCX_PAIR_PERSIST=0: one workgroup per tile with the wide epilogue (round 4's default, now the fallback of the persistent
-    form and the form of C = 256)."""
-    _run_mode({"RVCX_PAIR_PERSIST": "0"}, "test_gpu_conv.py", "fused_resblock", "10 passed")
+def test_fused_resblock_step_in_plain_tile_order_is_bit_identical_too():
+    """RVCX_PAIR_XCD=0: the fused ResBlock step hands out its tiles in plain order instead of giving each XCD
+    a contiguous range.  Every fused_resblock test of test_gpu_conv.py -- each shipped instantiation once, and the persistent
+    workgroups that walk several tiles -- must still equal the two conv launches bit for bit and torch within fp32 rounding."""
+    _run_mode({"RVCX_PAIR_XCD": "0"}, "test_gpu_conv.py", "fused_resblock", "23 passed")
 
 
 @pytest.mark.parametrize("env", [{"RVCX_GRU_FORM": "0"}, {"RVCX_GRU_FORM": "1"}, {"RVCX_GRU_COLOCATE": "0"},

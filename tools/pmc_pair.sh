@@ -1,9 +1,8 @@
 #!/bin/bash
-# PMC passes over the fused ResBlock step (tools/bench_pair.py shapes $1) for RVCX_PAIR_VARIANT=$2: LDS / wait / MFMA counters
+# PMC passes over the fused ResBlock step (tools/bench_pair.py shapes $1): LDS / wait / MFMA counters
 set -u
 cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
-[ -n "${2:-}" ] && export RVCX_PAIR_VARIANT=$2
 OUT=/tmp/pmc_pair_$$
 for set in "SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_DATA_FIFO_FULL SQ_LDS_CMD_FIFO_FULL SQ_LDS_ADDR_CONFLICT SQ_INSTS_LDS" \
            "SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY GRBM_GUI_ACTIVE SQ_INSTS_MFMA SQ_BUSY_CYCLES" \
