@@ -588,6 +588,79 @@ int rvcx_fx_chorus_host(const float* x, int64_t n, int sr, float rate_hz, float 
 int rvcx_fx_mix_host(const int16_t* vocal, int64_t n_v, const int16_t* inst, int64_t n_i, float vocal_gain_db,
                      float inst_gain_db, int16_t* out);
 
+/* ---- loudness, true peak, limiter, master ------------------------------------------------------------------------------
+ * Stages 9 - 12 continue "post-production": the signal, the rates and the error rules are that section's.  The loudness
+ * measure is ITU-R BS.1770-4 / EBU R 128 (Tech 3341 for the conformance signals); the limiter and the master are this
+ * project's own definitions.  Tested against float64 (tests/loudness_reference.py).
+ *
+ *  9 programme loudness L(x) in LUFS.  Per channel two biquads in series (transposed direct form II as stage 5), their
+ *    coefficients formed in double:
+ *      shelf: f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / sr), Vh = 10^(G/20),
+ *        Vb = Vh^0.4996667741545416, a0 = 1 + K/Q + K^2; b = {Vh + Vb K/Q + K^2, 2 (K^2 - Vh), Vh - Vb K/Q + K^2} / a0;
+ *        a1 = 2 (K^2 - 1) / a0, a2 = (1 - K/Q + K^2) / a0
+ *      high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773; b = {1, -2, 1} (not normalised), a1, a2 as above
+ *    (at 48 kHz the Recommendation's table to every printed digit).  The filter KEEPS double coefficients and double state
+ *    on the device and on the host, unlike stages 1, 5 and 6: 1 + a1 + a2 of the high-pass is 1.6e-6 at 192 kHz, below what
+ *    float32 coefficients resolve.  The float32 samples are widened, nothing else is rounded to float32.
+ *    h = sr / 10.  Hop sums s_c[k]: the squared filtered samples of [k h, (k+1) h) summed in double; only whole hops count.
+ *    Blocks j = 0 .. nb-1, nb = floor(n / h) - 3 (400 ms, 75 % overlap): z[j] = sum over channels of ((s_c[j] + s_c[j+1]) +
+ *    s_c[j+2]) + s_c[j+3], divided by 4 h; channel weights are 1.  l[j] = -0.691 + 10 log10 z[j] (the momentary values).
+ *    Absolute gate: l[j] > -70.  Gamma = -0.691 + 10 log10(mean of z over those blocks) - 10.  L = -0.691 + 10 log10(mean of
+ *    z over the blocks with l[j] > -70 and l[j] > Gamma); -infinity when nb < 1 or no block passes.
+ *    On the device the recurrence runs as the biquad scan does, on four states, and a hop's sum is put together from the
+ *    partial sums of the chunks it touches, in chunk order; the gated means are summed in an order fixed by nb alone.  A
+ *    result therefore depends on the item only -- not on B or the grouping -- and differs from the sequential host twin by
+ *    the association of double sums.
+ * 10 true peak TP(x) in dBTP: 4x oversampling by an interpolating Kaiser-windowed sinc, h(t) = sinc(t) I0(9 sqrt(1 - (t/12)^2))
+ *    / I0(9) for |t| < 12, else 0.  y[4n + p] = sum over m of x[n - m] h(m + p/4); x is zero outside the signal.  Phase 0 is
+ *    the sample itself.  Phases 1 - 3 have 24 taps each (m = -12 .. 11), formed in double and rounded once to float32, and are
+ *    accumulated from zero with fmaf in the order m = -12, -11, ..., 11 on both sides.  p[n] = max over channels and the four
+ *    phases of |y[4n + p]|, n = 0 .. len-1; TP = 20 log10 max p[n] (-infinity for silence).  Device = host twin bit for bit.
+ * 11 limiter (ceiling_db <= 0, lookahead_ms in 0 .. 10, release_ms in 0 .. 10000), channels linked.  c = fl(10^(ceiling_db/20));
+ *    r[n] = min(1, c / p[n]); W = floor(lookahead_ms sr / 1000); g[n] = min r[n .. n + W] (r = 1 past the end); e = the
+ *    follower of stage 2 on u = 1 - g with attack constant 0 and release cte(release_ms), where u is 1 - g rounded UP (the
+ *    smallest float32 with 1 - u <= g: to nearest, 1 - u could exceed g by 2^-25 once g < 0.5); q = 1 - e; s[n] = (q[n - W] + ... +
+ *    q[n], in double, an index below 0 taking q[0]) / (W + 1), rounded to float32; y = x s.  s[n] <= r[n] for every n, hence
+ *    |y[n]| <= c up to the last rounding; the true peak of y is not bounded by construction (measured: tests).  Skip: when
+ *    max p <= c nothing is launched and the output is the input bit for bit.  Device = host twin bit for bit (min is exact,
+ *    the follower is stage 2's, and q is a multiple of 2^-24, so the box sum is exact in double).
+ * 12 master: vocal (n_v, 2) and instrumental (n_i, 2) float32 at one rate; target_lufs <= 0, vocal_offset_lu, ceiling_dbtp <= 0.
+ *    The instrumental is cut or zero-padded to n_v first.  Lv, Li = stage 9 of the two.  gi = 10^((target - Li) / 20),
+ *    gv = 10^((target + offset - Lv) / 20), each formed in double and rounded once; a stem at -infinity keeps gain 1.
+ *    m = fl(gv V) + fl(gi I).  Lm = stage 9 of m; m is scaled by fl(10^((target - Lm) / 20)).  Stage 11 at the ceiling with
+ *    lookahead 2 ms and release 100 ms.  int16 = clip(rint(32768 y)).  report7 per item, in double: {Lv, Li, Lm, loudness of
+ *    y, TP in front of the limiter, TP of y, min s[n]} (y: the float result in front of the int16 rounding).
+ *    The three gains are formed on the host from the device's loudness values (one synchronisation each), so that the host
+ *    twin forms them with the same libm.
+ *
+ * Errors: a rate or channel count out of range, a value that is not finite, target or ceiling above 0, lookahead or release
+ * out of range return -1 with a message and write nothing. */
+/* blocks of stage 9 for n frames: max(0, floor(n / (sr / 10)) - 3) */
+int64_t rvcx_fx_momentary_len(int64_t n, int sr);
+/* stage 9 (and 10 when tp_db is given) on B items of `channels` channels.  lufs, tp_db: B doubles; momentary_hd (optional):
+ * per item rvcx_fx_momentary_len floats (an item without a block is not touched).  Groups as rvcx_fx_chain. */
+int rvcx_fx_loudness(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, int channels, int sr, double* lufs,
+                     double* tp_db, float* const* momentary_hd);
+/* stage 10 on one item; p_hd (optional): the n values p[n] */
+int rvcx_op_fx_truepeak(rvcx_ctx*, const float* x_hd, int64_t n, int channels, float* p_hd, double* tp_db);
+/* stage 11 on one item; gain_hd (optional): the n values s[n] (all 1 when the stage is skipped) */
+int rvcx_op_fx_limit(rvcx_ctx*, const float* x_hd, int64_t n, int channels, int sr, float ceiling_db, float lookahead_ms,
+                     float release_ms, float* y_hd, float* gain_hd);
+/* stage 12 on B covers: out_hd[b] receives (n_v[b], 2) int16; report7 (optional): B x 7 doubles.  n_i[b] may be 0 */
+int rvcx_fx_master(rvcx_ctx*, int B, const float* const* vocal_hd, const int64_t* n_v, const float* const* inst_hd,
+                   const int64_t* n_i, int sr, double target_lufs, double vocal_offset_lu, double ceiling_dbtp,
+                   int16_t* const* out_hd, double* report7);
+/* Host only, no context, no GPU.  coef10: {shelf b0, b1, b2, a1, a2, high-pass b0, b1, b2, a1, a2}; taps72: phases 1 - 3, 24 taps
+ * each, tap j of a phase multiplying x[n + 12 - j] */
+int rvcx_fx_kweight_coeffs(int sr, double* coef10);
+int rvcx_fx_truepeak_taps(float* taps72);
+int rvcx_fx_loudness_host(const float* x, int64_t n, int channels, int sr, double* lufs, float* momentary);
+int rvcx_fx_truepeak_host(const float* x, int64_t n, int channels, float* p, double* tp_db);
+int rvcx_fx_limit_host(const float* x, int64_t n, int channels, int sr, float ceiling_db, float lookahead_ms, float release_ms,
+                       float* y, float* gain);
+int rvcx_fx_master_host(const float* vocal, int64_t n_v, const float* inst, int64_t n_i, int sr, double target_lufs,
+                        double vocal_offset_lu, double ceiling_dbtp, int16_t* out, double* report7);
+
 /* ---- live post-production ---------------------------------------------------------------------------------------------
  * The board of "post-production" inside a live-stream session: rvcx_stream_open_fx puts stages 1 - 7 behind the output
  * resampler, inside the step, on the device, with all state carried from block to block.
@@ -655,7 +728,10 @@ int rvcx_fx_reverb_host(const float* x, int64_t n, int sr, float room_size, floa
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
  * {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} -- a session's input resampler is counted in the
  * F0 interval, its output resampler in "SOLA + copies"; of the last rvcx_fx_chain: {high-pass, compressor, gate, reverb, low
- * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups) */
+ * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups); of the last rvcx_fx_loudness: {copies +
+ * layout, chunk states, carry, K-weighting + energy, hop sums + gates, true peak, copies back, 0, total}; of the last
+ * rvcx_fx_master: {stem loudness, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters, copies +
+ * layout, total} */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration

@@ -170,6 +170,9 @@ SYMBOLS = [
     "rvcx_op_fx_chorus", "rvcx_op_fx_mix", "rvcx_fx_chunk", "rvcx_fx_last_passes", "rvcx_fx_cte", "rvcx_fx_delay",
     "rvcx_fx_coeffs", "rvcx_fx_highpass_host", "rvcx_fx_biquad_host", "rvcx_fx_follower_host", "rvcx_fx_compressor_host",
     "rvcx_fx_gate_host", "rvcx_fx_comb_host", "rvcx_fx_allpass_host", "rvcx_fx_chorus_host", "rvcx_fx_mix_host",
+    "rvcx_fx_momentary_len", "rvcx_fx_loudness", "rvcx_op_fx_truepeak", "rvcx_op_fx_limit", "rvcx_fx_master",
+    "rvcx_fx_kweight_coeffs", "rvcx_fx_truepeak_taps", "rvcx_fx_loudness_host", "rvcx_fx_truepeak_host", "rvcx_fx_limit_host",
+    "rvcx_fx_master_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -273,6 +276,17 @@ def lib() -> C.CDLL:
         _lib.rvcx_stream_set_fx.argtypes = [vp, i, vp]
         _lib.rvcx_stream_last_fx_ms.argtypes = [vp, i, vp]
         _lib.rvcx_op_stream_fx.argtypes = [vp, vp, i, i64, i, i, i, vp, C.c_uint32, vp]
+        _lib.rvcx_fx_momentary_len.argtypes, _lib.rvcx_fx_momentary_len.restype = [i64, i], i64
+        _lib.rvcx_fx_loudness.argtypes = [vp, i, vp, vp, i, i, vp, vp, vp]
+        _lib.rvcx_op_fx_truepeak.argtypes = [vp, vp, i64, i, vp, vp]
+        _lib.rvcx_op_fx_limit.argtypes = [vp, vp, i64, i, i, f, f, f, vp, vp]
+        _lib.rvcx_fx_master.argtypes = [vp, i, vp, vp, vp, vp, i, d, d, d, vp, vp]
+        _lib.rvcx_fx_kweight_coeffs.argtypes = [i, vp]
+        _lib.rvcx_fx_truepeak_taps.argtypes = [vp]
+        _lib.rvcx_fx_loudness_host.argtypes = [vp, i64, i, i, vp, vp]
+        _lib.rvcx_fx_truepeak_host.argtypes = [vp, i64, i, vp, vp]
+        _lib.rvcx_fx_limit_host.argtypes = [vp, i64, i, i, f, f, f, vp, vp]
+        _lib.rvcx_fx_master_host.argtypes = [vp, i64, vp, i64, i, d, d, d, vp, vp]
     return _lib
 
 
@@ -407,6 +421,83 @@ def fx_mix_host(vocal, inst, vocal_gain_db=0.0, inst_gain_db=0.0, out=None):
     _fx_host("fx_mix_host", lib().rvcx_fx_mix_host(v.ctypes.data, v.shape[0], m.ctypes.data, m.shape[0], float(vocal_gain_db),
                                                    float(inst_gain_db), y.ctypes.data))
     return y
+
+
+# ---- loudness, true peak, limiter, master on the host (rvcx.h stages 9 - 12) --------------------------------------------------
+MASTER_REPORT = ("vocal_lufs", "instrumental_lufs", "mix_lufs", "lufs", "true_peak_in_db", "true_peak_db", "min_gain")
+
+
+def _fx_sig(x, what):
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    if x.ndim not in (1, 2) or (x.ndim == 2 and x.shape[1] not in (1, 2)):
+        raise RvcxError(f"{what}: float array of shape (frames,) or (frames, 1 or 2) expected")
+    return x, (1 if x.ndim == 1 else x.shape[1])
+
+
+def _stereo_f32(a, what):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise RvcxError(f"{what}: float array of shape (frames, 2) expected")
+    return a
+
+
+def fx_momentary_len(n: int, sr: int) -> int:
+    """blocks of 400 ms at 75 % overlap in n frames"""
+    return int(lib().rvcx_fx_momentary_len(int(n), int(sr)))
+
+
+def fx_kweight_coeffs(sr: int) -> np.ndarray:
+    """float64 {shelf b0, b1, b2, a1, a2, high-pass b0, b1, b2, a1, a2} of the K-weighting filter"""
+    c = np.zeros(10, np.float64)
+    _fx_host("fx_kweight_coeffs", lib().rvcx_fx_kweight_coeffs(int(sr), c.ctypes.data))
+    return c
+
+
+def fx_truepeak_taps() -> np.ndarray:
+    """float32 (3, 24): phases 1 - 3 of the 4x interpolator; tap j of a phase multiplies x[n + 12 - j]"""
+    t = np.zeros((3, 24), np.float32)
+    _fx_host("fx_truepeak_taps", lib().rvcx_fx_truepeak_taps(t.ctypes.data))
+    return t
+
+
+def fx_loudness_host(x, sr, momentary=False):
+    """stage 9 sequentially -> LUFS (float, -inf without a block), or (LUFS, float32 momentary values)"""
+    x, ch = _fx_sig(x, "fx_loudness_host")
+    L = C.c_double()
+    m = np.zeros(max(fx_momentary_len(x.shape[0], sr), 1), np.float32) if momentary else None
+    _fx_host("fx_loudness_host", lib().rvcx_fx_loudness_host(x.ctypes.data, x.shape[0], ch, int(sr), C.byref(L),
+                                                             None if m is None else m.ctypes.data))
+    return (L.value, m[:fx_momentary_len(x.shape[0], sr)]) if momentary else L.value
+
+
+def fx_truepeak_host(x, want_p=False):
+    """stage 10 sequentially -> dBTP, or (dBTP, p[n])"""
+    x, ch = _fx_sig(x, "fx_truepeak_host")
+    tp = C.c_double()
+    p = np.zeros(max(x.shape[0], 1), np.float32) if want_p else None
+    _fx_host("fx_truepeak_host", lib().rvcx_fx_truepeak_host(x.ctypes.data, x.shape[0], ch, None if p is None else p.ctypes.data,
+                                                             C.byref(tp)))
+    return (tp.value, p[:x.shape[0]]) if want_p else tp.value
+
+
+def fx_limit_host(x, sr, ceiling_db=-1.0, lookahead_ms=2.0, release_ms=100.0, out=None):
+    """stage 11 sequentially -> (y, s[n])"""
+    x, ch = _fx_sig(x, "fx_limit_host")
+    y, g = _fx_out(x, out), np.ones(max(x.shape[0], 1), np.float32)
+    _fx_host("fx_limit_host", lib().rvcx_fx_limit_host(x.ctypes.data, x.shape[0], ch, int(sr), float(ceiling_db),
+                                                       float(lookahead_ms), float(release_ms), y.ctypes.data, g.ctypes.data))
+    return y, g[:x.shape[0]]
+
+
+def fx_master_host(vocal, inst, sr, target_lufs=-16.0, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, out=None):
+    """stage 12 sequentially -> ((n_v, 2) int16, report dict)"""
+    v, m = _stereo_f32(vocal, "fx_master_host"), _stereo_f32(inst, "fx_master_host")
+    y = np.zeros((v.shape[0], 2), np.int16) if out is None else out
+    rep = np.zeros(7, np.float64)
+    _fx_host("fx_master_host", lib().rvcx_fx_master_host(v.ctypes.data, v.shape[0], m.ctypes.data, m.shape[0], int(sr),
+                                                         float(target_lufs), float(vocal_offset_lu), float(ceiling_dbtp),
+                                                         y.ctypes.data, rep.ctypes.data))
+    return y, dict(zip(MASTER_REPORT, (float(r) for r in rep)))
 
 
 _device_info_cache = {}
@@ -1554,6 +1645,75 @@ class Context:
         lib().rvcx_last_timing(self._h, ms)
         names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "copies", "total"]
         return dict(zip(names, [float(v) for v in ms]))
+
+    # ---- loudness, true peak, limiter, master (rvcx.h stages 9 - 12) --------------------------------------------------------
+    def fx_loudness(self, items, sr, momentary=False):
+        """rvcx_fx_loudness on a list of signals of one rate and channel count in one call -> list of (LUFS, dBTP), with
+        momentary=True of (LUFS, dBTP, float32 momentary values)"""
+        xs = [self._fx_in(x) for x in items]
+        if not xs or any(ch != xs[0][1] for _, ch in xs):
+            raise RvcxError("fx_loudness: a non-empty list of items with one channel count expected")
+        B, ch = len(xs), xs[0][1]
+        xp = (C.c_void_p * B)(*[x.ctypes.data for x, _ in xs])
+        n = (C.c_int64 * B)(*[x.shape[0] for x, _ in xs])
+        L, tp = np.zeros(B, np.float64), np.zeros(B, np.float64)
+        ms = [np.zeros(max(fx_momentary_len(x.shape[0], sr), 1), np.float32) for x, _ in xs] if momentary else None
+        mp = (C.c_void_p * B)(*[m.ctypes.data for m in ms]) if momentary else None
+        self._ck(lib().rvcx_fx_loudness(self._h, B, xp, n, ch, int(sr), L.ctypes.data, tp.ctypes.data, mp), "fx_loudness")
+        if momentary:
+            return [(float(L[b]), float(tp[b]), ms[b][:fx_momentary_len(xs[b][0].shape[0], sr)]) for b in range(B)]
+        return [(float(L[b]), float(tp[b])) for b in range(B)]
+
+    def fx_loudness_timing(self):
+        """per-stage device ms of the last fx_loudness call"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["copies_in", "chunk_states", "carry", "kweight_energy", "gates", "true_peak", "copies_out", "unused", "total"]
+        return dict(zip(names, [float(v) for v in ms]))
+
+    def fx_master_timing(self):
+        """per-stage device ms of the last fx_master call"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["stem_loudness", "mix", "mix_loudness", "scale_true_peak", "limiter_gain", "gain_int16", "result_meters",
+                 "copies", "total"]
+        return dict(zip(names, [float(v) for v in ms]))
+
+    def fx_true_peak(self, x, want_p=False):
+        """rvcx_op_fx_truepeak -> dBTP, or (dBTP, p[n])"""
+        x, ch = self._fx_in(x)
+        tp = C.c_double()
+        p = np.zeros(x.shape[0], np.float32) if want_p else None
+        self._ck(lib().rvcx_op_fx_truepeak(self._h, x.ctypes.data, x.shape[0], ch, None if p is None else p.ctypes.data,
+                                           C.byref(tp)), "op_fx_truepeak")
+        return (tp.value, p) if want_p else tp.value
+
+    def fx_limit(self, x, sr, ceiling_db=-1.0, lookahead_ms=2.0, release_ms=100.0, want_gain=False):
+        """rvcx_op_fx_limit -> y, or (y, s[n])"""
+        x, ch = self._fx_in(x)
+        y, g = np.empty_like(x), (np.zeros(x.shape[0], np.float32) if want_gain else None)
+        self._ck(lib().rvcx_op_fx_limit(self._h, x.ctypes.data, x.shape[0], ch, int(sr), float(ceiling_db), float(lookahead_ms),
+                                        float(release_ms), y.ctypes.data, None if g is None else g.ctypes.data), "op_fx_limit")
+        return (y, g) if want_gain else y
+
+    def fx_master(self, vocals, insts, sr, target_lufs=-16.0, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
+        """rvcx_fx_master: lists of (n_v, 2) and (n_i, 2) float32 stems of one rate -> (list of (n_v, 2) int16, list of
+        report dicts)"""
+        vs = [_stereo_f32(v, "fx_master") for v in vocals]
+        ms = [_stereo_f32(m, "fx_master") for m in insts]
+        if not vs or len(vs) != len(ms) or any(v.shape[0] < 1 for v in vs):
+            raise RvcxError("fx_master: as many instrumentals as vocals, at least one, every vocal with a frame")
+        B = len(vs)
+        ys = [np.zeros((v.shape[0], 2), np.int16) for v in vs]
+        vp_ = (C.c_void_p * B)(*[v.ctypes.data for v in vs])
+        mp = (C.c_void_p * B)(*[m.ctypes.data if m.shape[0] else None for m in ms])
+        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        nv = (C.c_int64 * B)(*[v.shape[0] for v in vs])
+        ni = (C.c_int64 * B)(*[m.shape[0] for m in ms])
+        rep = np.zeros((B, 7), np.float64)
+        self._ck(lib().rvcx_fx_master(self._h, B, vp_, nv, mp, ni, int(sr), float(target_lufs), float(vocal_offset_lu),
+                                      float(ceiling_dbtp), yp, rep.ctypes.data), "fx_master")
+        return ys, [dict(zip(MASTER_REPORT, (float(r) for r in row))) for row in rep]
 
     def fx_highpass(self, x, sr, fc=50.0):
         x, ch = self._fx_in(x)

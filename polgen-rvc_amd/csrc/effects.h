@@ -7,6 +7,7 @@
 // sample, so a row's result depends on nothing but the row (and, for the reverb, its partner).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdint>
 
 namespace rvcx {
@@ -69,6 +70,54 @@ void fx_chorus_host(const FxChorus& ch, const float* x, long n, float* y);
 void fx_mix_host(const int16_t* v, long nv, const int16_t* inst, long ni, double gv, double gi, int16_t* out);
 // the whole reverb on one stereo item, x and y (n, 2) interleaved: fx_comb_host / fx_allpass_host and the mix FMAs
 void fx_reverb_host(const FxReverb& rv, const float* x, long n, float* y);
+
+// ---- loudness, true peak, limiter, master (loudness.hip; rvcx.h stages 9 - 12) ------------------------------------------------
+// The K-weighting filter keeps DOUBLE coefficients and state on both sides: 1 + a1 + a2 of its high-pass is 1.6e-6 at
+// 192 kHz, below what float32 coefficients resolve.
+struct FxKWeight {
+  double sb0, sb1, sb2, sa1, sa2;    // shelf
+  double hb0, hb1, hb2, ha1, ha2;    // high-pass (b = 1, -2, 1, not normalised)
+};
+FxKWeight fx_kweight(int sr);
+constexpr int kTpTaps = 24;          // taps of each non-trivial phase of the 4x interpolator (12 samples either way)
+struct FxTpTaps {
+  float h[3][kTpTaps];               // h[p - 1][j] = h(j - 12 + p / 4): the tap of x[n + 12 - j]; accumulated j = 0 .. 23
+};
+const FxTpTaps& fx_tp_taps();
+inline long fx_momentary_len(long n, int sr) { return std::max(0L, n / (sr / 10) - 3); }
+inline int fx_lookahead(int sr, double ms) { return (int)(ms * sr / 1000.0); }
+constexpr int kFxMaxLookahead = 1920;   // 10 ms at 192 kHz: what the sliding-minimum tile holds
+
+// L per item from planar rows (len: B * C ints, a row per channel).  scratch: fx_loudness_scratch_bytes.  lufs: B doubles on
+// the device; mom (optional): B rows of mom_ld floats.  ev (optional, 4 events): behind local, carry, apply + energy, gates.
+size_t fx_loudness_scratch_bytes(int B, int C, long ld, int sr);
+void launch_fx_loudness(const FxKWeight& k, const float* rows, const int* len, int B, int C, long ld, int sr, void* scratch,
+                        double* lufs, float* mom, long mom_ld, hipStream_t s, hipEvent_t* ev);
+// p[n] (optional: B rows of ld, one per ITEM) and the bits of max p per item (peak: B words, zeroed here)
+void launch_fx_truepeak(const float* rows, const int* len, int B, int C, long ld, float* p, uint32_t* peak, hipStream_t s);
+// s[n] of stage 11 from p: B rows of ld (ilen / ilen_host: B ints); u, e: B x ld scratch; state as launch_fx_follower's;
+// smin: the bits of min s per item (B words, set here).  Returns the follower's passes.
+int launch_fx_limit_gain(const float* p, const int* ilen, const int* ilen_host, int B, long ld, float c, int W, float c_rel,
+                         float* u, float* e, float* state, float* sgain, uint32_t* smin, hipStream_t s);
+// y = x s (sgain null: s = 1) -> planar y (optional, may be x), interleaved float stage (optional), interleaved int16 (optional)
+void launch_fx_limit_apply(const float* rows, const float* sgain, const int* len, int B, int C, long ld, float* y, float* stage,
+                           int16_t* pcm, hipStream_t s);
+// v = fl(gv v) + fl(gi inst) over len_v (inst zero past len_i); gv, gi: B floats on the device
+void launch_fx_master_mix(float* v, const float* inst, const int* len_v, const int* len_i, const float* gv, const float* gi, int B,
+                          int C, long ld, hipStream_t s);
+void launch_fx_scale(float* rows, const float* g, int B, int C, long ld, hipStream_t s);   // rows of item b times g[b]
+
+// host twins: x (n, C) interleaved.  mom (optional): fx_momentary_len floats.  p (optional): n floats.
+double fx_loudness_host(const FxKWeight& k, const float* x, long n, int C, int sr, float* mom);
+float fx_truepeak_host(const float* x, long n, int C, float* p);                  // max p[n] (0 when n == 0)
+void fx_limit_gain_host(const float* p, long n, float c, int W, float c_rel, float* sgain);
+double fx_db20(float peak);                                   // 20 log10, -infinity at 0
+double fx_gain_to(double target, double L);                   // 10^((target - L) / 20); 1 when L is not finite
+// stage 11 whole (peak_out: max p in front of the stage, smin_out: min s; both optional) and stage 12 whole, one item
+void fx_limit_host(const float* x, long n, int C, int sr, double ceiling_db, double lookahead_ms, double release_ms, float* y,
+                   float* gain, float* peak_out, float* smin_out);
+void fx_master_host(const float* vocal, long n_v, const float* inst, long n_i, int sr, double target_lufs, double vocal_offset_lu,
+                    double ceiling_dbtp, int16_t* out, double* report7);
 
 // ---- the board inside a live session (effects_live.hip; rvcx.h "live post-production") --------------------------------------
 // Every stage runs sequentially in sample order from state the session carries, so a step's output is the stage on the whole

@@ -51,6 +51,50 @@ __host__ __device__ inline int16_t fx_mix_sample(int v, int i, double gv, double
   return (int16_t)(t < -32768 ? -32768 : t > 32767 ? 32767 : t);
 }
 
+// ---- stages 9 - 12 ---------------------------------------------------------------------------------------------------------------
+// one sample through the shelf and the high-pass of the K-weighting filter, in double; st: the four states
+__host__ __device__ inline double fx_kw_step(const FxKWeight& k, double x, double* st) {
+  const double v = fma(k.sb0, x, st[0]);
+  st[0] = fma(k.sb1, x, fma(-k.sa1, v, st[1]));
+  st[1] = fma(k.sb2, x, -k.sa2 * v);
+  const double y = fma(k.hb0, v, st[2]);
+  st[2] = fma(k.hb1, v, fma(-k.ha1, y, st[3]));
+  st[3] = fma(k.hb2, v, -k.ha2 * y);
+  return y;
+}
+
+// z of a block from four hop sums per channel (s: the first of the four), channels in order; h: samples per hop
+__host__ __device__ inline double fx_block_z(const double* s, long stride, int C, long h) {
+  double z = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double* q = s + (long)c * stride;
+    z += ((q[0] + q[1]) + q[2]) + q[3];
+  }
+  return z / (4.0 * (double)h);
+}
+__host__ __device__ inline double fx_lufs(double z) { return -0.691 + 10.0 * log10(z); }
+
+// one phase of the interpolator at a sample: w[0] = x[n + 12] ... w[-23] = x[n - 11], taps j = 0 .. 23 in that order
+__host__ __device__ inline float fx_tp_phase(const float* w, const float* h) {
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < kTpTaps; ++j) acc = FX_FMA(w[-j], h[j], acc);
+  return acc;
+}
+
+// u = 1 - g rounded UP: the smallest float32 with 1 - u <= g.  Rounding to nearest can leave 1 - u above g by 2^-25 once
+// g < 0.5; with this u the limiter's bound s[n] <= r[n] holds in float32 as it does in exact arithmetic (1 - u is exact
+// for u >= 0.5, and for u < 0.5 the difference 1 - g was exact to begin with).
+__host__ __device__ inline float fx_one_minus_up(float g) {
+  const float u = FX_SUB(1.f, g);
+  return FX_SUB(1.f, u) > g ? nextafterf(u, 2.f) : u;
+}
+
+__host__ __device__ inline int16_t fx_pcm16(float y) {
+  const float v = rintf(FX_MUL(32768.f, y));
+  return (int16_t)(v < -32768.f ? -32768.f : v > 32767.f ? 32767.f : v);
+}
+
 // w[n]: the delay line d read at n - tau(n), linear interpolation, zero in front of sample 0
 // (Line: anything indexable by a global sample index -- a row, or a session's ring)
 template <typename Line>

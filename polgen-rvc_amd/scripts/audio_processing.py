@@ -9,6 +9,15 @@ and "flac" outputs work, any other ``output_format`` ("mp3", the tab's default, 
 missing encoder before any work is done.  ``progress`` is accepted and ignored.
 
 ``process_audio_many(jobs)`` is new: a list of covers whose boards run in ONE ``rvcx_fx_chain`` call per (rate, settings).
+
+Loudness (include/rvcx.h stages 9 - 12) is new as well.  ``measure_loudness(paths)`` reads LUFS and dBTP, one device call per
+rate.  ``combine_audio``, ``process_audio`` and ``process_audio_many`` take the keyword-only ``target_lufs=None,
+vocal_offset_lu=0.0, ceiling_dbtp=-1.0``: with ``target_lufs=None`` nothing changes (the int16 mix, byte for byte); with a
+value the stems go through ``rvcx_fx_master`` as float -- both brought to the target, the vocal ``vocal_offset_lu`` above the
+instrumental, the sum brought to the target again and limited to the ceiling.  The sliders ``vocal_gain`` /
+``instrumental_gain`` are then added, in dB, to the computed gains; since the sum is normalised afterwards, what remains of
+them is their difference, which moves the vocal against the instrumental.  ``last_master_report()`` returns the reports of
+the last such call.
 """
 from __future__ import annotations
 
@@ -21,7 +30,8 @@ from .. import _lib
 from ..infer import _state
 from ..infer.audio import convert_to_stereo, read_audio, write_output, write_wav_pcm16
 
-__all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "OUTPUT_DIR"]
+__all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "measure_loudness",
+           "last_master_report", "OUTPUT_DIR"]
 
 OUTPUT_DIR = os.path.join(os.getcwd(), "output")
 
@@ -54,10 +64,73 @@ def _effects(ctx, signals, sr, values):
         return ctx.fx_chain([np.ascontiguousarray(_stereo(x), dtype=np.float32) for x in signals], params)
 
 
-def combine_audio(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain, output_format):
-    """audio_processing.py:29-40: vocal + gain overlaid with instrumental + gain in int16, at the vocal's rate and length"""
+_reports = []
+
+
+def last_master_report():
+    """the reports of the last call that mastered (``target_lufs`` given), one dict per cover in the call's order: the keys
+    of ``_lib.MASTER_REPORT`` and ``"path"``"""
+    return [dict(r) for r in _reports]
+
+
+def measure_loudness(path_or_paths):
+    """-> [(LUFS, dBTP)] of one file or a list of files, as they are (mono or stereo); one rvcx_fx_loudness call per rate and
+    channel count"""
+    paths = [path_or_paths] if isinstance(path_or_paths, (str, os.PathLike)) else list(path_or_paths)
+    ctx = _state.context()
+    groups, out = {}, [None] * len(paths)
+    for i, path in enumerate(paths):
+        x, sr = read_audio(path)
+        x = np.asarray(x, np.float32)
+        x = x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
+        groups.setdefault((sr, 1 if x.ndim == 1 else x.shape[1]), []).append((i, x))
+    for (sr, _), members in groups.items():
+        with ctx.lock:
+            got = ctx.fx_loudness([x for _, x in members], sr)
+        for (i, _), r in zip(members, got):
+            out[i] = r
+    return out
+
+
+def _stems(ctx, vocal_path, instrumental_path):
+    """both files as float (frames, 2) at the vocal's rate"""
+    v, sr = read_audio(vocal_path)
+    m, sr_m = read_audio(instrumental_path)
+    v, m = _stereo(v), _stereo(m)
+    if sr_m != sr:
+        with ctx.lock:
+            m = np.stack([ctx.resample(m[:, c], sr_m, sr) for c in range(2)], axis=1)
+    return v, m, sr
+
+
+def _master(ctx, covers, target_lufs, vocal_offset_lu, ceiling_dbtp):
+    """covers: (vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain); one rvcx_fx_master call per
+    (rate, slider difference)"""
+    groups = {}
+    for k, (vp, ip, op, gv, gi) in enumerate(covers):
+        v, m, sr = _stems(ctx, vp, ip)
+        groups.setdefault((sr, float(gv) - float(gi)), []).append((k, op, np.asarray(v, np.float32), np.asarray(m, np.float32)))
+    reports = [None] * len(covers)
+    for (sr, slider), members in groups.items():
+        with ctx.lock:
+            outs, reps = ctx.fx_master([v for _, _, v, _ in members], [m for _, _, _, m in members], sr, target_lufs,
+                                       vocal_offset_lu + slider, ceiling_dbtp)
+        for (k, op, _, _), y, rep in zip(members, outs, reps):
+            write_output(op, y, sr)
+            reports[k] = dict(rep, path=op)
+    _reports[:] = reports
+
+
+def combine_audio(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain, output_format, *,
+                  target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
+    """audio_processing.py:29-40: vocal + gain overlaid with instrumental + gain in int16, at the vocal's rate and length;
+    with ``target_lufs`` the loudness-matched master of include/rvcx.h stage 12 instead"""
     _check_format(output_format)
     ctx = _state.context()
+    if target_lufs is not None:
+        _master(ctx, [(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain)], target_lufs,
+                vocal_offset_lu, ceiling_dbtp)
+        return
     v, sr = read_audio(vocal_path)
     m, sr_m = read_audio(instrumental_path)
     v, m = _stereo(v), _stereo(m)
@@ -98,7 +171,7 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
                   reverb_width, low_shelf_gain, high_shelf_gain, compressor_ratio, compressor_threshold,
                   noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
                   chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix, output_format, vocal_gain,
-                  instrumental_gain, use_effects, progress=None):
+                  instrumental_gain, use_effects, progress=None, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
     """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>"""
     _check_paths(vocal_audio_path, instrumental_audio_path)
     _check_format(output_format)
@@ -116,15 +189,17 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
                     chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix)
     else:
         vocal_output_path = voice_stereo_path
-    combine_audio(vocal_output_path, instrumental_audio_path, aicover_path, vocal_gain, instrumental_gain, output_format)
+    combine_audio(vocal_output_path, instrumental_audio_path, aicover_path, vocal_gain, instrumental_gain, output_format,
+                  target_lufs=target_lufs, vocal_offset_lu=vocal_offset_lu, ceiling_dbtp=ceiling_dbtp)
     return aicover_path
 
 
-def process_audio_many(jobs):
+def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
     """A list of covers in one go.  Every job is the positional argument tuple of ``process_audio`` (24 values; a 25th, when
     given, is the output path -- the default is OUTPUT_DIR/AiCover_<index>.<output_format>).  The boards of all jobs that
     share a sample rate and the eighteen effect values run in ONE rvcx_fx_chain call; every cover is byte for byte what
-    ``process_audio`` writes for the same arguments.  Returns the list of output paths."""
+    ``process_audio`` writes for the same arguments.  With ``target_lufs`` all covers of one rate (and one slider difference)
+    are mastered in ONE rvcx_fx_master call.  Returns the list of output paths."""
     jobs = [tuple(j) for j in jobs]
     for j in jobs:
         if len(j) not in (24, 25):
@@ -150,5 +225,9 @@ def process_audio_many(jobs):
         for i, j in enumerate(jobs):
             if os.path.exists(outs[i]):
                 os.remove(outs[i])
-            combine_audio(vocal[i], j[1], outs[i], j[21], j[22], j[20])
+            if target_lufs is None:
+                combine_audio(vocal[i], j[1], outs[i], j[21], j[22], j[20])
+        if target_lufs is not None:
+            _master(ctx, [(vocal[i], j[1], outs[i], j[21], j[22]) for i, j in enumerate(jobs)], target_lufs, vocal_offset_lu,
+                    ceiling_dbtp)
     return outs
