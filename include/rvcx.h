@@ -661,6 +661,61 @@ int rvcx_fx_limit_host(const float* x, int64_t n, int channels, int sr, float ce
 int rvcx_fx_master_host(const float* vocal, int64_t n_v, const float* inst, int64_t n_i, int sr, double target_lufs,
                         double vocal_offset_lu, double ceiling_dbtp, int16_t* out, double* report7);
 
+/* ---- time stretch and pitch shift ---------------------------------------------------------------------------------------
+ * Stages 13 and 14 continue "post-production" (signal, rates, error rules): the key change for a backing track.  A
+ * phase-locked vocoder (identity phase locking) whose phases are integers in units of 2^-32 turn, so that its frame-to-frame
+ * recurrence is an exact, associative scan: chunk length, segment length, batch and grouping change no bit.  The definition
+ * is this project's own; tested against float64 (tests/stretch_reference.py).
+ *
+ * 13 time stretch by P / Q, per channel; 1 <= Q <= 2^20, Q / 2 <= P <= 2 Q.  n_s = floor((n P + floor(Q / 2)) / Q) samples.
+ *    Geometry: N = the smallest power of two with 24 N >= sr (512 at 8 kHz .. 8192 at 192 kHz), H = N / 4, nb = N / 2 + 1,
+ *    w[i] = 0.5 - 0.5 cos(2 pi i / N) formed in double and rounded once.  Analysis frames t = 0 .. T - 1, T = floor(n / H) + 1:
+ *    D[t][k] = sum_i w[i] x[t H - N / 2 + i] e^(-2 pi i k i / N), x zero outside the signal, stored as float32 pairs; frames T
+ *    and T + 1 are all zero.
+ *    Per frame, from the float32 D: A2[k] = fl(fl(re re) + fl(im im)) (float32, no fma), A = sqrtf(A2), TH[k] =
+ *    rint((double) atan2f(im, re) 2^31 / pi) mod 2^32, 0 when A2 == 0.  k is a peak when A2[k] > 0, A2[k] > A2[k - 1],
+ *    A2[k] > A2[k - 2], A2[k] >= A2[k + 1], A2[k] >= A2[k + 2], a neighbour outside 0 .. nb - 1 counting as smaller.
+ *    own[k] = the peak nearest to k, the lower one at equal distance; own[k] = k in a frame without a peak.
+ *    Output frames j = 0 .. J - 1, J = ceil(T P / Q): t_j = floor(j Q / P), f_j = (j Q mod P) / P, M_j[k] = (1 - f_j) A[t_j][k]
+ *    + f_j A[t_j + 1][k], phase PHI_j = R_j + TH[t_j] mod 2^32 with R_0 = 0 and, p = own[t_{j+1}][k],
+ *      R_{j+1}[k] = R_j[own[t_j][p]] + TH[t_j + 1][p] - TH[t_{j+1}][p]  mod 2^32
+ *    (a map R -> R o par + off; such maps compose exactly).  At P = Q every offset is 0 and the stage returns its input to
+ *    rounding.  Synthesis: angle = (int32) PHI pi / 2^31, fr_j = w irfft(M_j e^(i PHI_j)) (scaling 1 / N),
+ *    y[m] = sum_j fr_j[m + N / 2 - j H] / sum_j w^2[m + N / 2 - j H] over the frames 0 <= j < J that cover m, in ascending j,
+ *    the divisor in double; 0 where the divisor is <= 1e-8.
+ *    On the device the transforms, M, the angle and the numerator are float32; the host twin transforms and synthesises in
+ *    double and rounds D, and y, once.  own is equal on both sides whenever D is, R whenever own and TH are (TH comes from
+ *    each side's own atan2f).
+ * 14 pitch shift by s semitones, |s| <= 12: P = floor(sr 2^(s / 12) + 0.5) formed in double, Q = sr; stage 13, then kaiser_hq
+ *    (rvcx_resample_f64_kind's kind 0, the same tap loop, float32 samples and a double sum) from rate P to rate sr per channel
+ *    plane, cut or zero-padded to n frames.  P == sr: the stage is skipped, nothing is launched, the output is the input bit
+ *    for bit.
+ *
+ * Errors: |s| > 12, P / Q out of range, a value that is not finite, a rate or channel count out of range return -1 with a
+ * message and write nothing. */
+int64_t rvcx_fx_stretch_len(int64_t n, int64_t P, int64_t Q);              /* n_s; -1 for a refused ratio */
+int rvcx_fx_stretch_frames(int64_t n, int sr, int64_t P, int64_t Q, int64_t* T, int64_t* J, int32_t* N);
+int64_t rvcx_fx_pitch_ratio(int sr, double semitones);                     /* P of stage 14; -1 when refused */
+int rvcx_fx_stretch_chunk(void);                                           /* output frames per chunk of the scan */
+/* stage 13 on B items of `channels` channels: y_hd[b] receives (rvcx_fx_stretch_len(n[b], P, Q), channels).  Groups as
+ * rvcx_fx_chain; long items run in segments of output frames with R and the overlap carried. */
+int rvcx_fx_stretch(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, int channels, int sr, int64_t P, int64_t Q,
+                    float* const* y_hd);
+/* stage 14 on B items: y_hd[b] receives (n[b], channels) */
+int rvcx_fx_pitch_shift(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, int channels, int sr, double semitones,
+                        float* const* y_hd);
+/* stage 13 on one channel of one item with its intermediates (each optional): D_hd (T + 2, nb, 2) float32, own_hd and TH_hd
+ * (T + 2, nb), R_hd (J, nb) */
+int rvcx_op_fx_stretch_taps(rvcx_ctx*, const float* x_hd, int64_t n, int sr, int64_t P, int64_t Q, float* y_hd, float* D_hd,
+                            int32_t* own_hd, uint32_t* TH_hd, uint32_t* R_hd);
+/* Host only, no context, no GPU.  The taps (optional) as above and for one channel only.  rvcx_fx_stretch_own_host: own of
+ * one frame from its nb float32 pairs D */
+int rvcx_fx_stretch_host(const float* x, int64_t n, int channels, int sr, int64_t P, int64_t Q, float* y, float* D, int32_t* own,
+                         uint32_t* TH, uint32_t* R);
+int rvcx_fx_pitch_shift_host(const float* x, int64_t n, int channels, int sr, double semitones, float* y, float* D, int32_t* own,
+                             uint32_t* TH, uint32_t* R);
+int rvcx_fx_stretch_own_host(const float* D, int nb, int32_t* own);
+
 /* ---- live post-production ---------------------------------------------------------------------------------------------
  * The board of "post-production" inside a live-stream session: rvcx_stream_open_fx puts stages 1 - 7 behind the output
  * resampler, inside the step, on the device, with all state carried from block to block.
@@ -731,7 +786,8 @@ int rvcx_fx_reverb_host(const float* x, int64_t n, int sr, float room_size, floa
  * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups); of the last rvcx_fx_loudness: {copies +
  * layout, chunk states, carry, K-weighting + energy, hop sums + gates, true peak, copies back, 0, total}; of the last
  * rvcx_fx_master: {stem loudness, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters, copies +
- * layout, total} */
+ * layout, total}; of the last rvcx_fx_stretch / rvcx_fx_pitch_shift: {copies + layout, transforms, owners, scan, inverse
+ * transforms, overlap-add, resampler, layout + copies back, total} (all zero when stage 14 was skipped) */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration
@@ -853,6 +909,9 @@ int rvcx_bench_conv1d(rvcx_ctx*, int B, int Cin, int Tin, int Cout, int K, int s
  * staging variant (ignored: the LDS-DMA variant was removed in round 2) and the split-K factor; -1 = heuristic.
  * Process-wide; never set by the product path. */
 int rvcx_conv_override(int tile, int variant, int splitk);
+/* test hook for stage 13: output frames per chunk of the scan and per segment, 0 = the default (refused like the hooks
+ * above).  No length changes a bit of any result. */
+int rvcx_fx_stretch_override(int chunk_frames, int segment_frames);
 /* ConvTranspose1d: w (Cin,Cout,K), padding p; Tout = (Tin-1)*s - 2p + K */
 int rvcx_op_convtranspose1d(rvcx_ctx*, const float* x, const float* w, const float* bias, float* y,
                             int B, int Cin, int Tin, int Cout, int K, int stride, int pad,

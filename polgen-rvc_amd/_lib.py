@@ -173,6 +173,9 @@ SYMBOLS = [
     "rvcx_fx_momentary_len", "rvcx_fx_loudness", "rvcx_op_fx_truepeak", "rvcx_op_fx_limit", "rvcx_fx_master",
     "rvcx_fx_kweight_coeffs", "rvcx_fx_truepeak_taps", "rvcx_fx_loudness_host", "rvcx_fx_truepeak_host", "rvcx_fx_limit_host",
     "rvcx_fx_master_host",
+    "rvcx_fx_stretch_len", "rvcx_fx_stretch_frames", "rvcx_fx_pitch_ratio", "rvcx_fx_stretch_chunk", "rvcx_fx_stretch",
+    "rvcx_fx_pitch_shift", "rvcx_op_fx_stretch_taps", "rvcx_fx_stretch_host", "rvcx_fx_pitch_shift_host",
+    "rvcx_fx_stretch_own_host", "rvcx_fx_stretch_override",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -287,6 +290,16 @@ def lib() -> C.CDLL:
         _lib.rvcx_fx_truepeak_host.argtypes = [vp, i64, i, vp, vp]
         _lib.rvcx_fx_limit_host.argtypes = [vp, i64, i, i, f, f, f, vp, vp]
         _lib.rvcx_fx_master_host.argtypes = [vp, i64, vp, i64, i, d, d, d, vp, vp]
+        _lib.rvcx_fx_stretch_len.argtypes, _lib.rvcx_fx_stretch_len.restype = [i64, i64, i64], i64
+        _lib.rvcx_fx_stretch_frames.argtypes = [i64, i, i64, i64, vp, vp, vp]
+        _lib.rvcx_fx_pitch_ratio.argtypes, _lib.rvcx_fx_pitch_ratio.restype = [i, d], i64
+        _lib.rvcx_fx_stretch.argtypes = [vp, i, vp, vp, i, i, i64, i64, vp]
+        _lib.rvcx_fx_pitch_shift.argtypes = [vp, i, vp, vp, i, i, d, vp]
+        _lib.rvcx_op_fx_stretch_taps.argtypes = [vp, vp, i64, i, i64, i64, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_stretch_host.argtypes = [vp, i64, i, i, i64, i64, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_pitch_shift_host.argtypes = [vp, i64, i, i, d, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_stretch_own_host.argtypes = [vp, i, vp]
+        _lib.rvcx_fx_stretch_override.argtypes = [i, i]
     return _lib
 
 
@@ -498,6 +511,84 @@ def fx_master_host(vocal, inst, sr, target_lufs=-16.0, vocal_offset_lu=0.0, ceil
                                                          float(target_lufs), float(vocal_offset_lu), float(ceiling_dbtp),
                                                          y.ctypes.data, rep.ctypes.data))
     return y, dict(zip(MASTER_REPORT, (float(r) for r in rep)))
+
+
+# ---- time stretch and pitch shift on the host (rvcx.h stages 13 and 14) ---------------------------------------------------------
+def fx_stretch_chunk() -> int:
+    """output frames per chunk of the stage-13 scan"""
+    return int(lib().rvcx_fx_stretch_chunk())
+
+
+def fx_stretch_len(n: int, P: int, Q: int) -> int:
+    """samples stage 13 returns for n: floor((n P + floor(Q / 2)) / Q); -1 for a refused ratio"""
+    return int(lib().rvcx_fx_stretch_len(int(n), int(P), int(Q)))
+
+
+def fx_stretch_frames(n: int, sr: int, P: int, Q: int):
+    """(T analysis frames, J output frames, N) of stage 13"""
+    T, J, N = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    _fx_host("fx_stretch_frames", lib().rvcx_fx_stretch_frames(int(n), int(sr), int(P), int(Q), C.byref(T), C.byref(J), C.byref(N)))
+    return int(T.value), int(J.value), int(N.value)
+
+
+def fx_pitch_ratio(sr: int, semitones: float) -> int:
+    """P of stage 14 (Q = sr): floor(sr 2^(s / 12) + 0.5); -1 when refused"""
+    return int(lib().rvcx_fx_pitch_ratio(int(sr), float(semitones)))
+
+
+def fx_stretch_override(chunk_frames: int = 0, segment_frames: int = 0):
+    """test hook (RVCX_DEBUG=1): chunk and segment length of stage 13 in output frames; 0 = the default"""
+    if lib().rvcx_fx_stretch_override(int(chunk_frames), int(segment_frames)) != 0:
+        raise RvcxError("fx_stretch_override: " + (lib().rvcx_last_error(None) or b"").decode())
+
+
+def _stretch_taps(n, sr, P, Q, want):
+    """arrays for the optional outputs D, own, TH, R of one channel"""
+    if not want:
+        return {}
+    T, J, N = fx_stretch_frames(n, sr, P, Q)
+    nb = N // 2 + 1
+    return dict(D=np.zeros((T + 2, nb, 2), np.float32), own=np.zeros((T + 2, nb), np.int32), TH=np.zeros((T + 2, nb), np.uint32),
+                R=np.zeros((J, nb), np.uint32))
+
+
+def _tap_ptrs(t):
+    return [t[k].ctypes.data if k in t else None for k in ("D", "own", "TH", "R")]
+
+
+def fx_stretch_host(x, sr, P, Q, taps=False):
+    """stage 13 on the host (FFT and synthesis in double) -> y, or (y, dict of D, own, TH, R) for a one-channel signal"""
+    x, ch = _fx_sig(x, "fx_stretch_host")
+    n = x.shape[0]
+    ns = max(fx_stretch_len(n, P, Q), 0)
+    y = np.zeros((ns,) + x.shape[1:], np.float32)
+    t = _stretch_taps(n, sr, P, Q, taps)
+    _fx_host("fx_stretch_host", lib().rvcx_fx_stretch_host(x.ctypes.data, n, ch, int(sr), int(P), int(Q), y.ctypes.data,
+                                                           *_tap_ptrs(t)))
+    return (y, t) if taps else y
+
+
+def fx_pitch_shift_host(x, sr, semitones, taps=False):
+    """stage 14 on the host -> y of x's shape, or (y, taps of its stage 13) for a one-channel signal"""
+    x, ch = _fx_sig(x, "fx_pitch_shift_host")
+    n = x.shape[0]
+    y = np.zeros_like(x)
+    P = fx_pitch_ratio(sr, semitones)
+    t = _stretch_taps(n, sr, P, sr, taps) if P > 0 and P != sr else {}
+    _fx_host("fx_pitch_shift_host", lib().rvcx_fx_pitch_shift_host(x.ctypes.data, n, ch, int(sr), float(semitones), y.ctypes.data,
+                                                                   *_tap_ptrs(t)))
+    return (y, t) if taps else y
+
+
+def fx_stretch_own_host(D):
+    """own of one frame (13.2) from its float32 spectrum: D (nb, 2) float pairs or a complex array of nb bins"""
+    D = np.asarray(D)
+    if np.iscomplexobj(D):
+        D = np.stack([D.real, D.imag], axis=-1)
+    D = np.ascontiguousarray(D, dtype=np.float32)
+    own = np.zeros(D.shape[0], np.int32)
+    _fx_host("fx_stretch_own_host", lib().rvcx_fx_stretch_own_host(D.ctypes.data, D.shape[0], own.ctypes.data))
+    return own
 
 
 _device_info_cache = {}
@@ -1714,6 +1805,54 @@ class Context:
         self._ck(lib().rvcx_fx_master(self._h, B, vp_, nv, mp, ni, int(sr), float(target_lufs), float(vocal_offset_lu),
                                       float(ceiling_dbtp), yp, rep.ctypes.data), "fx_master")
         return ys, [dict(zip(MASTER_REPORT, (float(r) for r in row))) for row in rep]
+
+    # ---- time stretch and pitch shift (rvcx.h stages 13 and 14) -------------------------------------------------------------
+    def _fx_items(self, items, what):
+        xs = [self._fx_in(x) for x in items]
+        if not xs or any(ch != xs[0][1] for _, ch in xs):
+            raise RvcxError(f"{what}: a non-empty list of items with one channel count expected")
+        B = len(xs)
+        xp = (C.c_void_p * B)(*[x.ctypes.data for x, _ in xs])
+        n = (C.c_int64 * B)(*[x.shape[0] for x, _ in xs])
+        return [x for x, _ in xs], xs[0][1], B, xp, n
+
+    def fx_stretch(self, items, sr, P, Q):
+        """rvcx_fx_stretch: a list of float32 signals of one rate and channel count, stretched by P / Q in one call"""
+        xs, ch, B, xp, n = self._fx_items(items, "fx_stretch")
+        ys = [np.zeros((max(fx_stretch_len(x.shape[0], P, Q), 1),) + x.shape[1:], np.float32) for x in xs]
+        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        self._ck(lib().rvcx_fx_stretch(self._h, B, xp, n, ch, int(sr), int(P), int(Q), yp), "fx_stretch")
+        return [y[:fx_stretch_len(x.shape[0], P, Q)] for x, y in zip(xs, ys)]
+
+    def fx_pitch_shift(self, items, sr, semitones):
+        """rvcx_fx_pitch_shift: every item shifted by `semitones` at its own length"""
+        xs, ch, B, xp, n = self._fx_items(items, "fx_pitch_shift")
+        ys = [np.zeros_like(x) for x in xs]
+        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        self._ck(lib().rvcx_fx_pitch_shift(self._h, B, xp, n, ch, int(sr), float(semitones), yp), "fx_pitch_shift")
+        return ys
+
+    def fx_stretch_taps(self, x, sr, P, Q):
+        """rvcx_op_fx_stretch_taps on one channel -> (y, dict of D (T + 2, nb, 2), own, TH (T + 2, nb) and R (J, nb))"""
+        x, ch = self._fx_in(x)
+        if ch != 1 or x.ndim != 1:
+            raise RvcxError("fx_stretch_taps: one channel of shape (frames,) expected")
+        n = x.shape[0]
+        if fx_stretch_len(n, P, Q) < 0:
+            raise RvcxError("fx_stretch_taps: 1 <= Q <= 2^20 and Q / 2 <= P <= 2 Q are required")
+        y = np.zeros(max(fx_stretch_len(n, P, Q), 1), np.float32)
+        t = _stretch_taps(n, sr, P, Q, True)
+        self._ck(lib().rvcx_op_fx_stretch_taps(self._h, x.ctypes.data, n, int(sr), int(P), int(Q), y.ctypes.data, *_tap_ptrs(t)),
+                 "op_fx_stretch_taps")
+        return y[:fx_stretch_len(n, P, Q)], t
+
+    def fx_stretch_timing(self):
+        """per-kernel device ms of the last fx_stretch / fx_pitch_shift call"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["copies_in", "transforms", "owners", "scan", "inverse_transforms", "overlap_add", "resampler", "copies_out",
+                 "total"]
+        return dict(zip(names, [float(v) for v in ms]))
 
     def fx_highpass(self, x, sr, fc=50.0):
         x, ch = self._fx_in(x)

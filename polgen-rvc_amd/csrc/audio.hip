@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "ops.h"
+#include "pitch.h"
 
 namespace rvcx {
 
@@ -57,11 +58,9 @@ long double bessel_i0(long double x) {          // power series: converges in < 
   return s;
 }
 
-// interp_win (right half of the filter) and interp_delta (its forward difference), optionally scaled by `gain`
-void build_window(const FilterSpec& F, double gain, std::vector<double>& win, std::vector<double>& delta) {
-  const int table = 1 << F.precision, n = F.zeros * table, nwin = n + 1;
-  win.resize(nwin);
-  delta.assign(nwin, 0.0);
+std::vector<double> make_base_window(const FilterSpec& F) {
+  const int table = 1 << F.precision, n = F.zeros * table;
+  std::vector<double> win((size_t)n + 1);
   const long double i0b = bessel_i0((long double)F.beta);
   const double pi = 3.14159265358979323846;
   for (int i = 0; i <= n; ++i) {
@@ -71,8 +70,29 @@ void build_window(const FilterSpec& F, double gain, std::vector<double>& win, st
     // np.kaiser(2 n + 1, beta)[n + i]: alpha = n, argument beta * sqrt(1 - (i / n)^2)
     const long double r = (long double)i / n;
     const long double taper = bessel_i0((long double)F.beta * sqrtl(std::max(0.0L, 1.0L - r * r))) / i0b;
-    win[i] = (double)taper * (F.rolloff * sinc) * gain;
+    win[i] = (double)taper * (F.rolloff * sinc);
   }
+  return win;
+}
+
+// the right half of the filter at gain 1, formed once per kind: 2e5 Bessel series in long double take 0.1 s, more than a whole
+// stage-14 call on the device
+const std::vector<double>& base_window(int kind) {
+  if (kind == 0) {
+    static const std::vector<double> hq = make_base_window(kSpecs[0]);
+    return hq;
+  }
+  static const std::vector<double> best = make_base_window(kSpecs[1]);
+  return best;
+}
+
+// interp_win (right half of the filter) and interp_delta (its forward difference), optionally scaled by `gain`
+void build_window(int kind, double gain, std::vector<double>& win, std::vector<double>& delta) {
+  const FilterSpec& F = kSpecs[kind];
+  const int table = 1 << F.precision, n = F.zeros * table, nwin = n + 1;
+  win = base_window(kind);
+  delta.assign(nwin, 0.0);
+  for (double& v : win) v *= gain;            // taper * (rolloff * sinc) * gain, in this order as before
   // exact tap positions: the last tap of a wing can lie within rounding of the window's edge, where a Kaiser window is not
   // zero (1e-8 of the peak) -- the final table sample is zero, so the weight runs out continuously (oracle/audio.py)
   if (F.exact) win[n] = 0.0;
@@ -84,7 +104,7 @@ void build_window(const FilterSpec& F, double gain, std::vector<double>& win, st
 // in front of n_orig.  X(i) is input sample i as a double.  The one-shot kernel and the streaming kernel below both call this
 // one function: what a session emits is the one-shot filter, tap for tap.
 template <typename TAcc, typename XF>
-__device__ __forceinline__ TAcc kaiser_exact_taps(const ResampleFilter& f, double time_register, long n_orig, XF X) {
+__host__ __device__ __forceinline__ TAcc kaiser_exact_taps(const ResampleFilter& f, double time_register, long n_orig, XF X) {
   const double* __restrict__ win = f.win;
   const double* __restrict__ delta = f.delta;
   const long n = (long)time_register;
@@ -241,7 +261,7 @@ ResampleFilter make_resample_filter_at(double* d, int sr_in, int sr_out, hipStre
   f.index_step = (int)(f.scale * f.table);
   RVCX_CHECK(f.index_step >= 1, "resample: ratio too small");
   std::vector<double> win, delta;
-  build_window(F, ratio < 1.0 ? ratio : 1.0, win, delta);
+  build_window(kind, ratio < 1.0 ? ratio : 1.0, win, delta);
   RVCX_HIP(hipMemcpyAsync(d, win.data(), (size_t)f.nwin * sizeof(double), hipMemcpyHostToDevice, s));
   RVCX_HIP(hipMemcpyAsync(d + f.nwin, delta.data(), (size_t)f.nwin * sizeof(double), hipMemcpyHostToDevice, s));
   RVCX_HIP(hipStreamSynchronize(s));          // the host vectors die with this frame
@@ -267,6 +287,32 @@ void launch_resample_f32(const ResampleFilter& f, const float* x, long n, float*
   // float32 in -> float32 out with a float32 running sum: what the published loop does on a float32 array
   hipLaunchKernelGGL((resample_kernel<float, float, float>), dim3((unsigned)cdiv64(n_out, 256)), dim3(256), 0, s, x, n, 1L, 1,
                      y, n_out, f);
+}
+
+// ---- one channel plane, float32 in and out, the running sum in double (rvcx.h stage 14): kaiser_hq, the same tap loop
+void launch_resample_plane_f32(const ResampleFilter& f, const float* x, long n, float* y, long n_out, hipStream_t s) {
+  RVCX_CHECK(f.exact, "resample plane: kaiser_hq only");
+  if (n_out <= 0) return;
+  hipLaunchKernelGGL((resample_kernel<float, float, double>), dim3((unsigned)cdiv64(n_out, 256)), dim3(256), 0, s, x, n, 1L, 1,
+                     y, n_out, f);
+}
+
+// the host path of the same plane: the tables of build_window in host memory, kaiser_exact_taps sample by sample
+void resample_plane_host(int sr_in, int sr_out, const float* x, long n, float* y, long n_out) {
+  const FilterSpec& F = kSpecs[0];
+  const double ratio = (double)sr_out / (double)sr_in;
+  std::vector<double> win, delta;
+  build_window(0, ratio < 1.0 ? ratio : 1.0, win, delta);
+  ResampleFilter f;
+  f.scale = std::min(1.0, ratio);
+  f.time_increment = 1.0 / ratio;
+  f.table = 1 << F.precision;
+  f.nwin = (int)win.size();
+  f.exact = 1;
+  f.win = win.data();
+  f.delta = delta.data();
+  for (long t = 0; t < n_out; ++t)
+    y[t] = (float)kaiser_exact_taps<double>(f, (double)t * f.time_increment, n, [&](long i) { return (double)x[i]; });
 }
 
 // ---- streaming: rules, geometry and the two launches of a step

@@ -18,6 +18,12 @@ instrumental, the sum brought to the target again and limited to the ceiling.  T
 ``instrumental_gain`` are then added, in dB, to the computed gains; since the sum is normalised afterwards, what remains of
 them is their difference, which moves the vocal against the instrumental.  ``last_master_report()`` returns the reports of
 the last such call.
+
+Key change (include/rvcx.h stages 13 and 14) is new too: the voice is transposed by ``pitch`` semitones in ``VC.pipeline``, the
+instrumental stays in the old key.  ``shift_pitch(input_path, output_path, semitones)`` transposes a file at its length and
+rate; the keyword-only ``instrumental_pitch=0.0`` of ``combine_audio``, ``process_audio`` and ``process_audio_many`` shifts the
+instrumental on the device in front of the mix (back to int16 by clip(rint(32768 y)); with ``target_lufs`` the float result
+goes to the master).  At 0.0 every file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -31,7 +37,7 @@ from ..infer import _state
 from ..infer.audio import convert_to_stereo, read_audio, write_output, write_wav_pcm16
 
 __all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "measure_loudness",
-           "last_master_report", "OUTPUT_DIR"]
+           "last_master_report", "shift_pitch", "OUTPUT_DIR"]
 
 OUTPUT_DIR = os.path.join(os.getcwd(), "output")
 
@@ -92,6 +98,29 @@ def measure_loudness(path_or_paths):
     return out
 
 
+def _shifted_many(ctx, items, sr, semitones):
+    """a list of signals of one rate and channel count shifted by `semitones` in ONE rvcx_fx_pitch_shift call -> float32"""
+    if not np.isfinite(semitones) or abs(semitones) > 12.0:
+        raise ValueError(f"pitch shift of {semitones!r} semitones: a finite value within -12 .. 12 is expected")
+    with ctx.lock:
+        return ctx.fx_pitch_shift([np.ascontiguousarray(x, dtype=np.float32) for x in items], sr, float(semitones))
+
+
+def _shifted(ctx, x, sr, semitones):
+    """x (frames,) or (frames, 1 or 2) shifted by `semitones` on the device -> float32, x's shape"""
+    return _shifted_many(ctx, [x], sr, semitones)[0]
+
+
+def shift_pitch(input_path, output_path, semitones):
+    """The file transposed by `semitones` (-12 .. 12) at its own length, rate and channel count (more than two channels: the
+    first two), written as 16-bit PCM through ``write_output``.  0 copies the samples."""
+    x, sr = read_audio(input_path)
+    x = np.asarray(x)
+    x = x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
+    y = _shifted(_state.context(), x, sr, semitones) if semitones else x
+    write_output(output_path, _pcm16(y), sr)
+
+
 def _stems(ctx, vocal_path, instrumental_path):
     """both files as float (frames, 2) at the vocal's rate"""
     v, sr = read_audio(vocal_path)
@@ -103,12 +132,26 @@ def _stems(ctx, vocal_path, instrumental_path):
     return v, m, sr
 
 
-def _master(ctx, covers, target_lufs, vocal_offset_lu, ceiling_dbtp):
+def _stems_many(ctx, pairs, instrumental_pitch=0.0):
+    """[(vocal_path, instrumental_path)] -> [(v, m, sr)]; with ``instrumental_pitch`` the instrumentals of one rate are
+    transposed in ONE rvcx_fx_pitch_shift call"""
+    stems = [_stems(ctx, vp, ip) for vp, ip in pairs]
+    if instrumental_pitch:
+        rates = {}
+        for k, (_, _, sr) in enumerate(stems):
+            rates.setdefault(sr, []).append(k)
+        for sr, members in rates.items():
+            for k, m in zip(members, _shifted_many(ctx, [stems[k][1] for k in members], sr, instrumental_pitch)):
+                stems[k] = (stems[k][0], m, sr)
+    return stems
+
+
+def _master(ctx, covers, target_lufs, vocal_offset_lu, ceiling_dbtp, instrumental_pitch=0.0):
     """covers: (vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain); one rvcx_fx_master call per
     (rate, slider difference)"""
     groups = {}
-    for k, (vp, ip, op, gv, gi) in enumerate(covers):
-        v, m, sr = _stems(ctx, vp, ip)
+    stems = _stems_many(ctx, [(vp, ip) for vp, ip, _, _, _ in covers], instrumental_pitch)
+    for k, ((_, _, op, gv, gi), (v, m, sr)) in enumerate(zip(covers, stems)):
         groups.setdefault((sr, float(gv) - float(gi)), []).append((k, op, np.asarray(v, np.float32), np.asarray(m, np.float32)))
     reports = [None] * len(covers)
     for (sr, slider), members in groups.items():
@@ -122,14 +165,15 @@ def _master(ctx, covers, target_lufs, vocal_offset_lu, ceiling_dbtp):
 
 
 def combine_audio(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain, output_format, *,
-                  target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
+                  target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, instrumental_pitch=0.0):
     """audio_processing.py:29-40: vocal + gain overlaid with instrumental + gain in int16, at the vocal's rate and length;
-    with ``target_lufs`` the loudness-matched master of include/rvcx.h stage 12 instead"""
+    with ``target_lufs`` the loudness-matched master of include/rvcx.h stage 12 instead; with ``instrumental_pitch`` the
+    instrumental is transposed first (stage 14)"""
     _check_format(output_format)
     ctx = _state.context()
     if target_lufs is not None:
         _master(ctx, [(vocal_path, instrumental_path, output_path, vocal_gain, instrumental_gain)], target_lufs,
-                vocal_offset_lu, ceiling_dbtp)
+                vocal_offset_lu, ceiling_dbtp, instrumental_pitch)
         return
     v, sr = read_audio(vocal_path)
     m, sr_m = read_audio(instrumental_path)
@@ -137,6 +181,8 @@ def combine_audio(vocal_path, instrumental_path, output_path, vocal_gain, instru
     with ctx.lock:
         if sr_m != sr:
             m = np.stack([ctx.resample(m[:, c], sr_m, sr) for c in range(2)], axis=1)
+        if instrumental_pitch:
+            m = _shifted(ctx, m, sr, instrumental_pitch)
         out = ctx.fx_mix(_pcm16(v), _pcm16(m), vocal_gain, instrumental_gain)
     write_output(output_path, out, sr)       # FLAC for a path ending in ".flac", WAV bytes otherwise
 
@@ -171,7 +217,8 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
                   reverb_width, low_shelf_gain, high_shelf_gain, compressor_ratio, compressor_threshold,
                   noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
                   chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix, output_format, vocal_gain,
-                  instrumental_gain, use_effects, progress=None, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
+                  instrumental_gain, use_effects, progress=None, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0,
+                  instrumental_pitch=0.0):
     """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>"""
     _check_paths(vocal_audio_path, instrumental_audio_path)
     _check_format(output_format)
@@ -190,16 +237,18 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
     else:
         vocal_output_path = voice_stereo_path
     combine_audio(vocal_output_path, instrumental_audio_path, aicover_path, vocal_gain, instrumental_gain, output_format,
-                  target_lufs=target_lufs, vocal_offset_lu=vocal_offset_lu, ceiling_dbtp=ceiling_dbtp)
+                  target_lufs=target_lufs, vocal_offset_lu=vocal_offset_lu, ceiling_dbtp=ceiling_dbtp,
+                  instrumental_pitch=instrumental_pitch)
     return aicover_path
 
 
-def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0):
+def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, instrumental_pitch=0.0):
     """A list of covers in one go.  Every job is the positional argument tuple of ``process_audio`` (24 values; a 25th, when
     given, is the output path -- the default is OUTPUT_DIR/AiCover_<index>.<output_format>).  The boards of all jobs that
     share a sample rate and the eighteen effect values run in ONE rvcx_fx_chain call; every cover is byte for byte what
     ``process_audio`` writes for the same arguments.  With ``target_lufs`` all covers of one rate (and one slider difference)
-    are mastered in ONE rvcx_fx_master call.  Returns the list of output paths."""
+    are mastered in ONE rvcx_fx_master call.  ``instrumental_pitch`` transposes the instrumentals, all of one rate in ONE rvcx_fx_pitch_shift call.  Returns the list of
+    output paths."""
     jobs = [tuple(j) for j in jobs]
     for j in jobs:
         if len(j) not in (24, 25):
@@ -225,9 +274,15 @@ def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_d
         for i, j in enumerate(jobs):
             if os.path.exists(outs[i]):
                 os.remove(outs[i])
-            if target_lufs is None:
+            if target_lufs is None and not instrumental_pitch:
                 combine_audio(vocal[i], j[1], outs[i], j[21], j[22], j[20])
+        if target_lufs is None and instrumental_pitch:      # the instrumentals of one rate in one call, then the int16 mixes
+            stems = _stems_many(ctx, [(vocal[i], j[1]) for i, j in enumerate(jobs)], instrumental_pitch)
+            for (i, j), (v, m, sr) in zip(enumerate(jobs), stems):
+                with ctx.lock:
+                    out = ctx.fx_mix(_pcm16(v), _pcm16(m), j[21], j[22])
+                write_output(outs[i], out, sr)
         if target_lufs is not None:
             _master(ctx, [(vocal[i], j[1], outs[i], j[21], j[22]) for i, j in enumerate(jobs)], target_lufs, vocal_offset_lu,
-                    ceiling_dbtp)
+                    ceiling_dbtp, instrumental_pitch)
     return outs
