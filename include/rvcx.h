@@ -716,6 +716,75 @@ int rvcx_fx_pitch_shift_host(const float* x, int64_t n, int channels, int sr, do
                              uint32_t* TH, uint32_t* R);
 int rvcx_fx_stretch_own_host(const float* D, int nb, int32_t* own);
 
+/* ---- noise reduction -----------------------------------------------------------------------------------------------------
+ * Stage 15 continues "post-production" (signal, rates, error rules): a soft spectral gate that takes room noise, hiss or the
+ * bleed of a separated stem out from under the voice, from a noise profile (mode 0) or adaptively (mode 1).  The gate decision
+ * is a sigmoid on a smoothed level, so it is continuous in the spectrum: no threshold flips a bin between float32 and float64.
+ * The definition is this project's own (noisereduce is the model for its two modes; parity with it is unpinned); tested
+ * against float64 (tests/denoise_reference.py).
+ *
+ * 15 noise reduction, per channel.  N, H = N / 4, nb = N / 2 + 1 and w are stage 13's.  Frames t = 0 .. T - 1, T = floor(n / H)
+ *    + 1; D[t][k] as in stage 13 (frame centred at t H, x zero outside the signal, float32 pairs); A2[t][k] = fl(fl(re re) +
+ *    fl(im im)), no fma.
+ *    Smoothed power S.  nf = floor(freq_smooth_hz N / (2 sr)) bins, nt = floor(time_smooth_ms sr / (2000 H)) frames; triangles
+ *    wf[i] = nf + 1 - |i|, |i| <= nf, and wt likewise.  S[t][k] = (sum_dt wt[dt] (sum_dk wf[dk] A2[t + dt][k + dk])) / ((sum_dt
+ *    wt[dt]) (sum_dk wf[dk])), every sum over the indices inside 0 .. T - 1 and 0 .. nb - 1 only (renormalised at the edges), in
+ *    float32 from zero, each in ascending index order, every product and sum rounded (no fma); the divisor is an integer below
+ *    2^24.  nf = 0 or nt = 0 leaves that axis alone.  nf > 64 or nt > 16 is refused.  Device = host twin bit for bit on a given A2.
+ *    mode 0, profile: l[t][k] = fl(10 log10f(fl(S + 1e-20f))).  The profile frames are those of a noise clip of the same rate and
+ *    channel count, through the same analysis and smoothing on its own grid, channel c of the clip serving channel c of the
+ *    item.  WITHOUT a clip the profile frames are the item's own: everything stationary in the item is then treated as noise.
+ *    mu[k], sd[k]: mean and population standard deviation of l over the Tp profile frames, two passes in double (sum of l, then
+ *    sum of (l - mu)^2), each as partial sums over 64 consecutive frames added in ascending order.  thr = mu + n_std sd (double);
+ *    m = 1 / (1 + expf(-z)), z = (float)((l - thr) / knee_db) formed in double.
+ *    mode 1, adaptive: A = sqrtf(S), c = exp(-H / (sr time_constant_s)) in double.  f[t] = (1 - c) A[t] + c f[t - 1], f[-1] =
+ *    A[0]; b[t] = (1 - c) f[t] + c b[t + 1], b[T] = f[T - 1]; both in double, per bin, two products and one sum each.  r = (A - b)
+ *    / (b + 1e-10); m = 1 / (1 + expf(-z)), z = (float)((r - thresh_mult) slope) formed in double.  A tone that holds steady
+ *    becomes the floor and is removed with it: that is the mode's documented property (a noise gate for speech and song
+ *    between pauses, not for drones).
+ *    Gain and synthesis: g = fl(1 - fl(strength fl(1 - m))), Y = g D (the imaginary parts of bins 0 and N / 2 dropped), fr_t =
+ *    w irfft(Y_t) (scaling 1 / N), y[i] = sum_t fr_t[i + N / 2 - t H] / sum_t w^2[i + N / 2 - t H] over the frames that cover i in
+ *    ascending t, the divisor in double; 0 where the divisor is <= 1e-8.  The output has n frames.
+ *    On the device the transforms and the numerator are float32; the host twin transforms and synthesises in double and rounds
+ *    D, and y, once, and applies the float32 roundings of A2, S, l and m as defined.
+ *    Skip: strength == 0 launches nothing, the output is the input bit for bit.
+ *    A result depends on the item and its noise clip alone: B, the grouping, RVCX_MAX_BATCH and the other members change no bit.
+ *
+ * Errors: a value out of the ranges below or not finite, a rate or channel count out of range, a noise clip in mode 1, n < 1
+ * return -1 with a message and write nothing.  An item that does not fit the arena budget on its own is refused with a
+ * message that names its size (one item is not cut into segments). */
+typedef struct {
+  int32_t sample_rate, channels;
+  int32_t mode;                 /* 0 profile, 1 adaptive (default 1) */
+  float strength;               /* 0 .. 1 (0.7) */
+  float n_std;                  /* mode 0: 0 .. 10 (3) */
+  float knee_db;                /* mode 0: 0.1 .. 20 (1) */
+  float thresh_mult;            /* mode 1: 0 .. 20 (1) */
+  float slope;                  /* mode 1: 0.1 .. 100 (5) */
+  float time_constant_s;        /* mode 1: 0.05 .. 30 (2) */
+  float freq_smooth_hz;         /* >= 0 (500) */
+  float time_smooth_ms;         /* >= 0 (50) */
+} rvcx_fx_denoise_params;
+/* T and N of an item of n frames, and the half-widths nf, nt of the default smoothing (500 Hz, 50 ms) at this rate */
+int rvcx_fx_denoise_frames(int64_t n, int sr, int64_t* T, int32_t* N, int32_t* nf, int32_t* nt);
+/* frames and bins of a smoothing tile and profile frames per partial sum: the lengths at which the kernels take another path */
+int rvcx_fx_denoise_tiles(int32_t* tile_t, int32_t* tile_k, int32_t* stat_chunk);
+/* stage 15 on B items of params->channels channels: y_hd[b] receives (n[b], channels).  noise_hd may be NULL, and so may any
+ * entry of it; noise_hd[b] holds (n_noise[b], channels).  Items that name the same clip share its analysis.  Groups as
+ * rvcx_fx_chain. */
+int rvcx_fx_denoise(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, const float* const* noise_hd,
+                    const int64_t* n_noise, const rvcx_fx_denoise_params*, float* const* y_hd);
+/* stage 15 on one channel of one item with its intermediates (each optional): D_hd (T, nb, 2) float32, S_hd (T, nb), mu_hd and
+ * sd_hd (nb doubles, mode 0), b_hd (T, nb) doubles (mode 1), m_hd (T, nb) */
+int rvcx_op_fx_denoise_taps(rvcx_ctx*, const float* x_hd, int64_t n, const float* noise_hd, int64_t n_noise,
+                            const rvcx_fx_denoise_params*, float* y_hd, float* D_hd, float* S_hd, double* mu_hd, double* sd_hd,
+                            double* b_hd, float* m_hd);
+/* Host only, no context, no GPU.  The taps (optional) as above and for one channel only.  rvcx_fx_denoise_smooth_host: S of a
+ * given (T, nb) array A2 */
+int rvcx_fx_denoise_host(const float* x, int64_t n, const float* noise, int64_t n_noise, const rvcx_fx_denoise_params*, float* y,
+                         float* D, float* S, double* mu, double* sd, double* b, float* m);
+int rvcx_fx_denoise_smooth_host(const float* A2, int64_t T, int nb, int nf, int nt, float* S);
+
 /* ---- live post-production ---------------------------------------------------------------------------------------------
  * The board of "post-production" inside a live-stream session: rvcx_stream_open_fx puts stages 1 - 7 behind the output
  * resampler, inside the step, on the device, with all state carried from block to block.
@@ -787,7 +856,9 @@ int rvcx_fx_reverb_host(const float* x, int64_t n, int sr, float room_size, floa
  * layout, chunk states, carry, K-weighting + energy, hop sums + gates, true peak, copies back, 0, total}; of the last
  * rvcx_fx_master: {stem loudness, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters, copies +
  * layout, total}; of the last rvcx_fx_stretch / rvcx_fx_pitch_shift: {copies + layout, transforms, owners, scan, inverse
- * transforms, overlap-add, resampler, layout + copies back, total} (all zero when stage 14 was skipped) */
+ * transforms, overlap-add, resampler, layout + copies back, total} (all zero when stage 14 was skipped); of the last
+ * rvcx_fx_denoise: {copies in + layout, analysis, smoothing, statistics (mode 0) or floor + mask (mode 1), mask (mode 0),
+ * synthesis, overlap-add, copies back, total} (all zero when stage 15 was skipped) */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration

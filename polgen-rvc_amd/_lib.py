@@ -176,6 +176,8 @@ SYMBOLS = [
     "rvcx_fx_stretch_len", "rvcx_fx_stretch_frames", "rvcx_fx_pitch_ratio", "rvcx_fx_stretch_chunk", "rvcx_fx_stretch",
     "rvcx_fx_pitch_shift", "rvcx_op_fx_stretch_taps", "rvcx_fx_stretch_host", "rvcx_fx_pitch_shift_host",
     "rvcx_fx_stretch_own_host", "rvcx_fx_stretch_override",
+    "rvcx_fx_denoise_frames", "rvcx_fx_denoise_tiles", "rvcx_fx_denoise", "rvcx_op_fx_denoise_taps", "rvcx_fx_denoise_host",
+    "rvcx_fx_denoise_smooth_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -300,6 +302,12 @@ def lib() -> C.CDLL:
         _lib.rvcx_fx_pitch_shift_host.argtypes = [vp, i64, i, i, d, vp, vp, vp, vp, vp]
         _lib.rvcx_fx_stretch_own_host.argtypes = [vp, i, vp]
         _lib.rvcx_fx_stretch_override.argtypes = [i, i]
+        _lib.rvcx_fx_denoise_frames.argtypes = [i64, i, vp, vp, vp, vp]
+        _lib.rvcx_fx_denoise_tiles.argtypes = [vp, vp, vp]
+        _lib.rvcx_fx_denoise.argtypes = [vp, i, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_op_fx_denoise_taps.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_denoise_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_denoise_smooth_host.argtypes = [vp, i64, i, i, i, vp]
     return _lib
 
 
@@ -589,6 +597,97 @@ def fx_stretch_own_host(D):
     own = np.zeros(D.shape[0], np.int32)
     _fx_host("fx_stretch_own_host", lib().rvcx_fx_stretch_own_host(D.ctypes.data, D.shape[0], own.ctypes.data))
     return own
+
+
+# ---- noise reduction on the host (rvcx.h stage 15) -------------------------------------------------------------------------------
+class FxDenoiseParams(C.Structure):
+    """rvcx_fx_denoise_params; make() fills the defaults of include/rvcx.h stage 15"""
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("mode", C.c_int32), ("strength", C.c_float),
+                ("n_std", C.c_float), ("knee_db", C.c_float), ("thresh_mult", C.c_float), ("slope", C.c_float),
+                ("time_constant_s", C.c_float), ("freq_smooth_hz", C.c_float), ("time_smooth_ms", C.c_float)]
+    DEFAULTS = dict(mode=1, strength=0.7, n_std=3.0, knee_db=1.0, thresh_mult=1.0, slope=5.0, time_constant_s=2.0,
+                    freq_smooth_hz=500.0, time_smooth_ms=50.0)
+    MODES = {"profile": 0, "adaptive": 1}
+
+    @classmethod
+    def make(cls, sr, channels=1, **values):
+        unknown = set(values) - set(cls.DEFAULTS)
+        if unknown:
+            raise RvcxError(f"FxDenoiseParams: unknown value(s) {sorted(unknown)}")
+        v = dict(cls.DEFAULTS, **values)
+        v["mode"] = cls.MODES.get(v["mode"], v["mode"])
+        return cls(int(sr), int(channels), int(v["mode"]), *[float(v[k]) for k in list(cls.DEFAULTS)[1:]])
+
+    def with_shape(self, sr, channels):
+        return type(self)(int(sr), int(channels), *[getattr(self, k) for k in self.DEFAULTS])
+
+
+def fx_denoise_frames(n: int, sr: int):
+    """(T frames, N, nf, nt) of stage 15 for n frames at sr; nf and nt are those of the default smoothing widths"""
+    T, N, nf, nt = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _fx_host("fx_denoise_frames", lib().rvcx_fx_denoise_frames(int(n), int(sr), C.byref(T), C.byref(N), C.byref(nf), C.byref(nt)))
+    return int(T.value), int(N.value), int(nf.value), int(nt.value)
+
+
+def fx_denoise_tiles():
+    """(frames per smoothing tile, bins per smoothing tile, profile frames per partial sum of the statistics)"""
+    a, b, c = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    lib().rvcx_fx_denoise_tiles(C.byref(a), C.byref(b), C.byref(c))
+    return int(a.value), int(b.value), int(c.value)
+
+
+def _denoise_taps(n, params, want):
+    """arrays for the optional outputs of one channel: D, S, m and mu, sd (mode 0) or b (mode 1)"""
+    if not want:
+        return {}
+    T, N, _, _ = fx_denoise_frames(n, params.sample_rate)
+    nb = N // 2 + 1
+    t = dict(D=np.zeros((T, nb, 2), np.float32), S=np.zeros((T, nb), np.float32), m=np.zeros((T, nb), np.float32))
+    if params.mode == 0:
+        t.update(mu=np.zeros(nb, np.float64), sd=np.zeros(nb, np.float64))
+    elif params.mode == 1:
+        t.update(b=np.zeros((T, nb), np.float64))
+    return t
+
+
+def _denoise_tap_ptrs(t):
+    return [t[k].ctypes.data if k in t else None for k in ("D", "S", "mu", "sd", "b", "m")]
+
+
+def _denoise_clip(noise, ch, what):
+    """a noise clip as float32 of the item's channel count, or None"""
+    if noise is None:
+        return None
+    z, zc = _fx_sig(noise, what)
+    if zc != ch:
+        raise RvcxError(f"{what}: the noise clip has {zc} channel(s), the item {ch}")
+    if z.shape[0] < 1:
+        raise RvcxError(f"{what}: a noise clip needs at least one frame")
+    return z
+
+
+def fx_denoise_host(x, sr, params=None, noise=None, taps=False):
+    """stage 15 on the host (transforms and synthesis in double) -> y, or (y, dict of taps) for a one-channel signal"""
+    x, ch = _fx_sig(x, "fx_denoise_host")
+    p = (params or FxDenoiseParams.make(sr, ch)).with_shape(sr, ch)
+    z = _denoise_clip(noise, ch, "fx_denoise_host")
+    y = np.zeros_like(x)
+    t = _denoise_taps(x.shape[0], p, taps)
+    _fx_host("fx_denoise_host", lib().rvcx_fx_denoise_host(x.ctypes.data, x.shape[0], None if z is None else z.ctypes.data,
+                                                           0 if z is None else z.shape[0], C.byref(p), y.ctypes.data,
+                                                           *_denoise_tap_ptrs(t)))
+    return (y, t) if taps else y
+
+
+def fx_denoise_smooth_host(A2, nf, nt):
+    """the smoothing of stage 15 alone on a (T, nb) float32 array"""
+    A2 = np.ascontiguousarray(A2, dtype=np.float32)
+    if A2.ndim != 2:
+        raise RvcxError("fx_denoise_smooth_host: an array of shape (T, nb) expected")
+    S = np.zeros_like(A2)
+    _fx_host("fx_denoise_smooth_host", lib().rvcx_fx_denoise_smooth_host(A2.ctypes.data, A2.shape[0], A2.shape[1], int(nf), int(nt),
+                                                                         S.ctypes.data))
+    return S
 
 
 _device_info_cache = {}
@@ -1852,6 +1951,46 @@ class Context:
         lib().rvcx_last_timing(self._h, ms)
         names = ["copies_in", "transforms", "owners", "scan", "inverse_transforms", "overlap_add", "resampler", "copies_out",
                  "total"]
+        return dict(zip(names, [float(v) for v in ms]))
+
+    # ---- noise reduction (rvcx.h stage 15) -------------------------------------------------------------------------------------
+    def fx_denoise(self, items, sr, params=None, noise=None):
+        """rvcx_fx_denoise: a list of float32 signals of one rate and channel count in one call -> list of arrays.  noise:
+        one array for all items, or a list with one entry (an array or None) per item"""
+        xs, ch, B, xp, n = self._fx_items(items, "fx_denoise")
+        p = (params or FxDenoiseParams.make(sr, ch)).with_shape(sr, ch)
+        if noise is None or isinstance(noise, np.ndarray):
+            clips = [_denoise_clip(noise, ch, "fx_denoise")] * B
+        else:
+            clips = [_denoise_clip(z, ch, "fx_denoise") for z in noise]
+            if len(clips) != B:
+                raise RvcxError("fx_denoise: one noise entry per item expected")
+        ys = [np.zeros_like(x) for x in xs]
+        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        zp = (C.c_void_p * B)(*[None if z is None else z.ctypes.data for z in clips])
+        zn = (C.c_int64 * B)(*[0 if z is None else z.shape[0] for z in clips])
+        self._ck(lib().rvcx_fx_denoise(self._h, B, xp, n, zp, zn, C.byref(p), yp), "fx_denoise")
+        return ys
+
+    def fx_denoise_taps(self, x, sr, params=None, noise=None):
+        """rvcx_op_fx_denoise_taps on one channel -> (y, dict of D (T, nb, 2), S, m (T, nb) and mu, sd (nb) or b (T, nb))"""
+        x, ch = self._fx_in(x)
+        if ch != 1 or x.ndim != 1:
+            raise RvcxError("fx_denoise_taps: one channel of shape (frames,) expected")
+        p = (params or FxDenoiseParams.make(sr, 1)).with_shape(sr, 1)
+        z = _denoise_clip(noise, 1, "fx_denoise_taps")
+        y = np.zeros_like(x)
+        t = _denoise_taps(x.shape[0], p, True)
+        self._ck(lib().rvcx_op_fx_denoise_taps(self._h, x.ctypes.data, x.shape[0], None if z is None else z.ctypes.data,
+                                               0 if z is None else z.shape[0], C.byref(p), y.ctypes.data, *_denoise_tap_ptrs(t)),
+                 "op_fx_denoise_taps")
+        return y, t
+
+    def fx_denoise_timing(self):
+        """per-kernel device ms of the last fx_denoise call"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["copies_in", "analysis", "smoothing", "stats_or_floor", "mask", "synthesis", "overlap_add", "copies_out", "total"]
         return dict(zip(names, [float(v) for v in ms]))
 
     def fx_highpass(self, x, sr, fc=50.0):

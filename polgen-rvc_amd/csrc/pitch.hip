@@ -25,6 +25,8 @@
 // A2 and M are defined with every rounding written out
 #pragma clang fp contract(off)
 
+#include "fft_device.h"
+
 namespace rvcx {
 
 namespace {
@@ -34,23 +36,6 @@ constexpr int kMaxNb = 4097;
 
 __device__ __forceinline__ long row_T(const FxStretchDev& d, int r) { return (long)d.len[r] / d.g.H + 1; }
 __device__ __forceinline__ long row_J(const FxStretchDev& d, long T) { return (T * d.P + d.Q - 1) / d.Q; }
-
-// in place on a[0 .. N) in LDS, input in bit-reversed order: decimation in time, e^(-2 pi i ..) twiddles
-__device__ __forceinline__ void fft_lds(float2* a, const float2* __restrict__ tw, int N, int logN) {
-  for (int st = 0; st < logN; ++st) {
-    const int half = 1 << st;
-    __syncthreads();
-    for (int b = threadIdx.x; b < N / 2; b += 256) {
-      const int pos = b & (half - 1), i0 = ((b >> st) << (st + 1)) + pos, i1 = i0 + half;
-      const float2 w = tw[pos << (logN - 1 - st)];
-      const float2 u = a[i0], v = a[i1];
-      const float tx = w.x * v.x - w.y * v.y, ty = w.x * v.y + w.y * v.x;
-      a[i0] = make_float2(u.x + tx, u.y + ty);
-      a[i1] = make_float2(u.x - tx, u.y - ty);
-    }
-  }
-  __syncthreads();
-}
 
 __global__ __launch_bounds__(256) void stretch_fft_kernel(const FxStretchDev d, const float* __restrict__ rows) {
   extern __shared__ float2 a[];
@@ -272,17 +257,7 @@ __global__ __launch_bounds__(256) void stretch_ola_kernel(const FxStretchDev d, 
   const long m = max(0L, s0 * H - N / 2) + (long)blockIdx.x * 256 + threadIdx.x;
   const long m1 = s1 >= J ? ns : min(ns, s1 * H - N / 2);
   if (m < 0 || m >= m1) return;
-  const long jlo = max(0L, (m - N / 2 + H) / H), jhi = min(J - 1, (m + N / 2) / H);
-  const float* fr = d.fr + (size_t)r * (d.S + 3) * N;
-  float num = 0.f;
-  double den = 0.0;
-  for (long j = jlo; j <= jhi; ++j) {
-    const long i = m + N / 2 - j * H;
-    if (i < 0 || i >= N) continue;                    // (never: the bounds of jlo and jhi)
-    num += fr[(size_t)(j - s0 + 3) * N + i];
-    den += (double)d.w[i] * (double)d.w[i];
-  }
-  y[(size_t)r * ld_y + m] = den > 1e-8 ? (float)((double)num / den) : 0.f;
+  y[(size_t)r * ld_y + m] = ola_gather(d.fr + (size_t)r * (d.S + 3) * N, 3 - s0, (size_t)N, d.w, m, J, N, H);
 }
 
 }  // namespace
@@ -333,27 +308,6 @@ void launch_stretch_segment(const FxStretchDev& d, long s0, float* y, long ld_y,
 namespace {
 
 using cplx = std::complex<double>;
-
-// forward transform in double, in place, natural order in and out
-void fft_host(std::vector<cplx>& a, const std::vector<cplx>& tw) {
-  const int N = (int)a.size();
-  int logN = 0;
-  while ((1 << logN) < N) ++logN;
-  for (int i = 0; i < N; ++i) {
-    int j = 0;
-    for (int b = 0; b < logN; ++b) j |= ((i >> b) & 1) << (logN - 1 - b);
-    if (j > i) std::swap(a[i], a[j]);
-  }
-  for (int st = 0; st < logN; ++st) {
-    const int half = 1 << st;
-    for (int b = 0; b < N / 2; ++b) {
-      const int pos = b & (half - 1), i0 = ((b >> st) << (st + 1)) + pos, i1 = i0 + half;
-      const cplx t = tw[(size_t)pos << (logN - 1 - st)] * a[i1];
-      a[i1] = a[i0] - t;
-      a[i0] += t;
-    }
-  }
-}
 
 }  // namespace
 

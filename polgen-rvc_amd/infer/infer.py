@@ -231,37 +231,93 @@ def load_audio(file, sample_rate, *, device=None):
     return np.asarray(audio, np.float64).flatten()
 
 
+_CLEAN = (None, "input", "output", "both")
+
+
+def _clean_check(clean_audio, clean_strength):
+    if clean_audio not in _CLEAN:
+        raise ValueError(f"clean_audio={clean_audio!r}: None, 'input', 'output' or 'both' is expected")
+    if clean_audio is not None and not (np.isfinite(clean_strength) and 0.0 <= clean_strength <= 1.0):
+        raise ValueError(f"clean_strength={clean_strength!r}: a value within 0 .. 1 is expected")
+
+
+def _cleaned(hubert_model, x, sr, strength):
+    """float32 mono at sr through the adaptive spectral gate (include/rvcx.h stage 15) on the resident context"""
+    ctx = hubert_model.ctx
+    with ctx.lock:
+        return ctx.fx_denoise([np.ascontiguousarray(x, dtype=np.float32)], sr,
+                              _lib.FxDenoiseParams.make(sr, 1, mode="adaptive", strength=float(strength)))[0]
+
+
+def _clean_input(hubert_model, audio, clean_audio, clean_strength):
+    """the 16 kHz mono signal between load_audio and VC.pipeline"""
+    if clean_audio in ("input", "both"):
+        return _cleaned(hubert_model, audio, 16000, clean_strength).astype(np.float64)
+    return audio
+
+
+def _clean_output(hubert_model, audio_opt, tgt_sr, clean_audio, clean_strength):
+    """the int16 result as float32 / 32768 at tgt_sr -> clip(rint(32768 y))"""
+    if clean_audio in ("output", "both"):
+        y = _cleaned(hubert_model, np.asarray(audio_opt, np.float32) / np.float32(32768.0), tgt_sr, clean_strength)
+        return np.clip(np.rint(32768.0 * y.astype(np.float64)), -32768, 32767).astype(np.int16)
+    return audio_opt
+
+
 def rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g,
               filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
               f0_max=1100):
     """rvc/infer/infer.py:109-153: load -> vc.pipeline -> WAV bytes whatever the extension -- except ".flac", which gets a
-    real FLAC stream (audio.write_output)."""
+    real FLAC stream (audio.write_output).  The reference's signature, to the name; the "clean audio" switch
+    of the UIs is ``rvc_infer_clean``."""
+    _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g, filter_radius, tgt_sr,
+               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, None, 0.7)
+
+
+def rvc_infer_clean(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g,
+                    filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
+                    f0_max=1100, *, clean_audio="input", clean_strength=0.7):
+    """``rvc_infer`` with noise reduction (include/rvcx.h stage 15, adaptive mode) on the device.  clean_audio: ``None``
+    (the bytes ``rvc_infer`` writes), ``"input"`` (the 16 kHz mono signal between ``load_audio`` and ``VC.pipeline``),
+    ``"output"`` (the int16 result as float32 / 32768 at ``tgt_sr``, back by clip(rint(32768 y))) or ``"both"``."""
+    _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g, filter_radius, tgt_sr,
+               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength)
+
+
+def _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g, filter_radius, tgt_sr,
+               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength):
     from .audio import write_output
-    audio = load_audio(input_path, 16000)
+    _clean_check(clean_audio, clean_strength)
+    audio = _clean_input(hubert_model, load_audio(input_path, 16000), clean_audio, clean_strength)
     pitch_guidance = cpt.get("f0", 1)
     audio_opt = vc.pipeline(hubert_model, net_g, 0, audio, input_path, pitch, f0_method, index_path, index_rate,
                             pitch_guidance, filter_radius, tgt_sr, 0, volume_envelope, version, protect,
                             hop_length, f0_file=None, f0_min=f0_min, f0_max=f0_max)
+    audio_opt = _clean_output(hubert_model, audio_opt, tgt_sr, clean_audio, clean_strength)
     # infer.py:153: sf.write(output_path, audio_opt, tgt_sr, format="WAV") -- a WAV whatever the extension says
     write_output(output_path, audio_opt, tgt_sr)
 
 
 def rvc_infer_many(index_path, index_rate, input_paths, output_paths, pitch, f0_method, cpt, version, net_g,
                    filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
-                   f0_max=1100):
+                   f0_max=1100, *, clean_audio=None, clean_strength=0.7):
     """``rvc_infer`` over lists of paths (the reference lists batch conversion as not done, TODO.md:11) through
     ``VC.pipeline_stream``: two conversions are in flight while the next file is decoded, and every output file holds
     the bytes ``rvc_infer`` writes for it.  A file that is not at 16 kHz is resampled on the GPU by ``load_audio``; the
     resampler is the one entry point of the context that does not complete the conversions in flight first (it works in
-    a buffer of its own on the front stream, beside their synthesizer)."""
+    a buffer of its own on the front stream, beside their synthesizer).  ``clean_audio`` / ``clean_strength``: as in
+    ``rvc_infer_clean``, every file holding the bytes that function writes for it; with ``None`` nothing changes.  (The
+    cleaning is an entry point like any other: it completes the conversions in flight first.)"""
     from .audio import write_output
+    _clean_check(clean_audio, clean_strength)
     input_paths, output_paths = list(input_paths), list(output_paths)
     if len(input_paths) != len(output_paths):
         raise ValueError("rvc_infer_many: one output path per input path")
     pitch_guidance = cpt.get("f0", 1)
-    clips = (load_audio(path, 16000) for path in input_paths)          # lazy: decoded as the stream asks for them
+    # lazy: decoded as the stream asks for them
+    clips = (_clean_input(hubert_model, load_audio(path, 16000), clean_audio, clean_strength) for path in input_paths)
     results = vc.pipeline_stream(hubert_model, net_g, 0, clips, None, pitch, f0_method, index_path, index_rate,
                                  pitch_guidance, filter_radius, tgt_sr, 0, volume_envelope, version, protect,
                                  hop_length, f0_file=None, f0_min=f0_min, f0_max=f0_max)
     for out_path, audio_opt in zip(output_paths, results):
-        write_output(out_path, audio_opt, tgt_sr)
+        write_output(out_path, _clean_output(hubert_model, audio_opt, tgt_sr, clean_audio, clean_strength), tgt_sr)

@@ -24,6 +24,13 @@ instrumental stays in the old key.  ``shift_pitch(input_path, output_path, semit
 rate; the keyword-only ``instrumental_pitch=0.0`` of ``combine_audio``, ``process_audio`` and ``process_audio_many`` shifts the
 instrumental on the device in front of the mix (back to int16 by clip(rint(32768 y)); with ``target_lufs`` the float result
 goes to the master).  At 0.0 every file is byte for byte what it was.
+
+Noise reduction (include/rvcx.h stage 15) is the "clean audio" switch of the UIs, which call noisereduce there: a soft spectral
+gate on the device, this project's own definition (parity with noisereduce is unpinned).  ``reduce_noise(input_path,
+output_path, strength)`` cleans a file at its length, rate and channel count, adaptively or from a noise clip
+(``mode="profile", noise_path=...``); ``reduce_noise_many(jobs)`` runs one device call per (rate, channel count).  The
+keyword-only ``vocal_denoise=0.0`` of ``process_audio`` and ``process_audio_many`` cleans the vocal in adaptive mode in front
+of the board; at 0.0 every file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -37,7 +44,7 @@ from ..infer import _state
 from ..infer.audio import convert_to_stereo, read_audio, write_output, write_wav_pcm16
 
 __all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "measure_loudness",
-           "last_master_report", "shift_pitch", "OUTPUT_DIR"]
+           "last_master_report", "shift_pitch", "reduce_noise", "reduce_noise_many", "OUTPUT_DIR"]
 
 OUTPUT_DIR = os.path.join(os.getcwd(), "output")
 
@@ -119,6 +126,77 @@ def shift_pitch(input_path, output_path, semitones):
     x = x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
     y = _shifted(_state.context(), x, sr, semitones) if semitones else x
     write_output(output_path, _pcm16(y), sr)
+
+
+def _two_channels(x):
+    x = np.asarray(x)
+    return x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
+
+
+def _denoise_params(sr, channels, strength, mode, params):
+    if mode not in _lib.FxDenoiseParams.MODES:
+        raise ValueError(f"noise reduction mode {mode!r}: 'adaptive' or 'profile' is expected")
+    if not (np.isfinite(strength) and 0.0 <= strength <= 1.0):
+        raise ValueError(f"noise reduction strength {strength!r}: a value within 0 .. 1 is expected")
+    try:
+        p = _lib.FxDenoiseParams.make(sr, channels, mode=mode, strength=float(strength), **params)
+        _lib.fx_denoise_host(np.zeros(1, np.float32), sr, p)         # the refusals of the library, on one sample of silence
+    except _lib.RvcxError as e:
+        raise ValueError(str(e)) from None
+    return p
+
+
+def _clip_for(noise_path, sr, channels):
+    """the noise clip of a job as float32, at the item's rate and channel count"""
+    if noise_path is None:
+        return None
+    z, sr_z = read_audio(noise_path)
+    z = np.asarray(_two_channels(z), np.float32)
+    if sr_z != sr or (1 if z.ndim == 1 else z.shape[1]) != channels:
+        raise ValueError(f"noise clip {noise_path!r}: {sr_z} Hz, {1 if z.ndim == 1 else z.shape[1]} channel(s); the file to "
+                         f"clean has {sr} Hz, {channels} channel(s)")
+    return z
+
+
+def reduce_noise_many(jobs, strength=0.7, *, mode="adaptive", noise_path=None, **params):
+    """jobs: (input_path, output_path) or (input_path, output_path, noise_path) tuples; ``noise_path=`` is the clip of the
+    jobs that name none (mode "profile" only; without any clip the file's own frames are the profile).  Every file keeps its
+    length, rate and channel count (more than two channels: the first two) and is written as 16-bit PCM through
+    ``write_output``; ONE rvcx_fx_denoise call per (rate, channel count).  ``params``: n_std, knee_db, thresh_mult, slope,
+    time_constant_s, freq_smooth_hz, time_smooth_ms.  Strength 0 copies the samples.  Returns the output paths."""
+    jobs = [tuple(j) for j in jobs]
+    if any(len(j) not in (2, 3) for j in jobs):
+        raise ValueError("reduce_noise_many: a job is (input_path, output_path) or (input_path, output_path, noise_path)")
+    groups = {}
+    for i, j in enumerate(jobs):
+        x, sr = read_audio(j[0])
+        x = np.asarray(_two_channels(x), np.float32)
+        ch = 1 if x.ndim == 1 else x.shape[1]
+        clip_path = j[2] if len(j) == 3 and j[2] is not None else noise_path
+        if clip_path is not None and mode != "profile":
+            raise ValueError("a noise clip needs mode='profile'")
+        _denoise_params(sr, ch, strength, mode, params)              # every refusal before the first file is written
+        groups.setdefault((sr, ch), []).append((i, x, _clip_for(clip_path, sr, ch)))
+    ctx = _state.context() if strength else None
+    for (sr, ch), members in groups.items():
+        if strength:
+            with ctx.lock:
+                ys = ctx.fx_denoise([x for _, x, _ in members], sr, _denoise_params(sr, ch, strength, mode, params),
+                                    noise=[z for _, _, z in members])
+        else:
+            ys = [x for _, x, _ in members]
+        for (i, _, _), y in zip(members, ys):
+            write_output(jobs[i][1], _pcm16(y), sr)
+    return [j[1] for j in jobs]
+
+
+def reduce_noise(input_path, output_path, strength=0.7, *, mode="adaptive", noise_path=None, **params):
+    """The file cleaned by the spectral gate of include/rvcx.h stage 15 at its own length, rate and channel count, written as
+    16-bit PCM through ``write_output``.  mode "adaptive" follows a noise floor per bin (a tone that holds steady for seconds
+    becomes the floor and goes with it); mode "profile" takes its thresholds from ``noise_path``, a recording of the noise
+    alone at the file's rate and channel count -- without one from the file's own frames, so that everything stationary in it
+    counts as noise.  Strength 0 copies the samples."""
+    reduce_noise_many([(input_path, output_path)], strength, mode=mode, noise_path=noise_path, **params)
 
 
 def _stems(ctx, vocal_path, instrumental_path):
@@ -218,8 +296,9 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
                   noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
                   chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix, output_format, vocal_gain,
                   instrumental_gain, use_effects, progress=None, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0,
-                  instrumental_pitch=0.0):
-    """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>"""
+                  instrumental_pitch=0.0, vocal_denoise=0.0):
+    """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>.  ``vocal_denoise``
+    (0 .. 1): the stereo vocal is cleaned in adaptive mode (``reduce_noise``) in front of the board"""
     _check_paths(vocal_audio_path, instrumental_audio_path)
     _check_format(output_format)
     os.makedirs(OUTPUT_DIR, exist_ok=True)
@@ -228,6 +307,8 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
     if os.path.exists(aicover_path):
         os.remove(aicover_path)
     convert_to_stereo(vocal_audio_path, voice_stereo_path)
+    if vocal_denoise:
+        reduce_noise(voice_stereo_path, voice_stereo_path, vocal_denoise)
     if use_effects:
         vocal_output_path = os.path.join(OUTPUT_DIR, "Vocal_Effected.wav")
         add_effects(voice_stereo_path, vocal_output_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping,
@@ -242,13 +323,15 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
     return aicover_path
 
 
-def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, instrumental_pitch=0.0):
+def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, instrumental_pitch=0.0,
+                       vocal_denoise=0.0):
     """A list of covers in one go.  Every job is the positional argument tuple of ``process_audio`` (24 values; a 25th, when
     given, is the output path -- the default is OUTPUT_DIR/AiCover_<index>.<output_format>).  The boards of all jobs that
     share a sample rate and the eighteen effect values run in ONE rvcx_fx_chain call; every cover is byte for byte what
     ``process_audio`` writes for the same arguments.  With ``target_lufs`` all covers of one rate (and one slider difference)
-    are mastered in ONE rvcx_fx_master call.  ``instrumental_pitch`` transposes the instrumentals, all of one rate in ONE rvcx_fx_pitch_shift call.  Returns the list of
-    output paths."""
+    are mastered in ONE rvcx_fx_master call.  ``instrumental_pitch`` transposes the instrumentals, all of one rate in ONE rvcx_fx_pitch_shift call.
+    ``vocal_denoise`` cleans the stereo vocals in front of the boards, all of one rate in ONE rvcx_fx_denoise call.  Returns the
+    list of output paths."""
     jobs = [tuple(j) for j in jobs]
     for j in jobs:
         if len(j) not in (24, 25):
@@ -263,6 +346,9 @@ def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_d
         for i, j in enumerate(jobs):
             vocal.append(os.path.join(tmp, f"Voice_Stereo_{i}.wav"))
             convert_to_stereo(j[0], vocal[i])
+        if vocal_denoise:
+            reduce_noise_many([(v, v) for v in vocal], vocal_denoise)
+        for i, j in enumerate(jobs):
             if j[23]:
                 x, sr = read_audio(vocal[i])
                 groups.setdefault((sr, tuple(float(v) for v in j[2:20])), []).append((i, x))
