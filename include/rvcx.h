@@ -847,11 +847,119 @@ int rvcx_op_stream_fx(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int c
 int rvcx_fx_reverb_host(const float* x, int64_t n, int sr, float room_size, float damping, float wet, float dry, float width,
                         float* y);
 
+/* ---- live noise reduction -------------------------------------------------------------------------------------------------
+ * Stage 16 is stage 15 made causal, so that a live-stream session can run it inside a step, at either edge: on the 16 kHz mono
+ * block in front of the ring (a microphone in a room feeds HuBERT and the F0 model directly) and on what leaves, behind the
+ * output resampler and in front of the board.  Stage 15 cannot run there: its adaptive floor runs backward from the end of the
+ * item and its time triangle reads frames that have not arrived.  The definition is this project's own; tested against float64
+ * (tests/denoise_live_reference.py).
+ *
+ * 16 live noise reduction, one channel, defined on x[0 .. ): everything the stream has received since open or reset.  There is
+ *    no last frame.  sr a multiple of 100 Hz in 3200 .. 192000.
+ *    Geometry: N = the smallest power of two with 48 N >= sr, and never below 512 (512 up to 24 kHz, 1024 at 44.1 and 48 kHz,
+ *    2048 at 96 kHz, 4096 at 192 kHz), H = N / 4, nb = N / 2 + 1, w[i] = 0.5 - 0.5 cos(2 pi i / N) formed in double and rounded
+ *    once (stage 13's formula at this N).
+ *    Frames t = 0, 1, ..: D[t][k] = sum_i w[i] x[t H - N / 2 + i] e^(-2 pi i k i / N), x = 0 in front of sample 0, float32 pairs;
+ *    A2[t][k] = fl(fl(re re) + fl(im im)), no fma.  Frame t is complete once sample t H + N / 2 - 1 has arrived: n samples
+ *    complete T(n) = floor((n - N / 2) / H) + 1 frames, none while n < N / 2.
+ *    Smoothed power S.  nf = floor(freq_smooth_hz N / (2 sr)) bins, wf[i] = nf + 1 - |i|, |i| <= nf: F[t][k] = sum_dk wf[dk]
+ *    A2[t][k + dk] over the bins inside 0 .. nb - 1, in float32 from zero in ascending k + dk, every product and sum rounded.
+ *    nt = floor(time_smooth_ms sr / (1000 H)) frames ON THE PAST SIDE ONLY, wt[dt] = nt + 1 - |dt|, dt = -nt .. 0: S[t][k] =
+ *    (sum_dt wt[dt] F[t + dt][k]) / ((sum_dt wt[dt]) (sum_dk wf[dk])), the sum over the frames t + dt >= 0 in float32 from zero
+ *    in ascending t + dt, the weight sums over the same indices; the divisor is an integer below 2^24, converted to float32,
+ *    and the quotient is one float32 division.  nf = 0 or nt = 0 leaves that axis alone.  nf > 64 or nt > 32 is refused.
+ *    mode 1, adaptive floor, forward only, per bin, in double: A = sqrtf(S), c_up = exp(-H / (sr time_constant_s)), c_dn =
+ *    exp(-H / (sr fall_time_s)); f[-1] = A[0]; f[t] = (1 - c) A[t] + c f[t - 1] with c = c_up when A[t] >= f[t - 1] and c_dn
+ *    otherwise (two products and one sum; 1 - c is formed in double).  The floor rises slowly under a voice and falls fast
+ *    into a pause; both branches give f[t - 1] at A[t] == f[t - 1], so f is continuous in the spectrum.  r = (A - f) / (f +
+ *    1e-10); m = 1 / (1 + expf(-z)), z = (float)((r - thresh_mult) slope) formed in double (stage 15's rule with f for b).
+ *    mode 0, profile: mu[k], sd[k] from a noise clip given at open (same rate, one channel, N / 2 .. 2^22 samples): the frames
+ *    of the clip are the Tp = T(n_noise) frames complete inside it, through this analysis and this smoothing from sample 0 of
+ *    the clip; l = fl(10 log10f(fl(S + 1e-20f))); mean and population standard deviation of l over the Tp frames as in stage 15
+ *    (two passes in double, partial sums over 64 consecutive frames added in ascending order); thr = mu + n_std sd; m = 1 /
+ *    (1 + expf(-z)), z = (float)((l - thr) / knee_db) formed in double.  Mode 0 without a clip is refused, and so is a clip
+ *    in mode 1.
+ *    Gain and synthesis: g = fl(1 - fl(strength fl(1 - m))), Y = g D (the imaginary parts of bins 0 and N / 2 dropped), fr_t =
+ *    w irfft(Y_t) (scaling 1 / N); y[i] = (sum_t fr_t[i + N / 2 - t H]) / (sum_t w^2[i + N / 2 - t H]) over all frames t >= 0
+ *    that cover i, each sum in ascending t; the numerator in float32 from zero, the divisor in double (it is never below 1 and
+ *    has period H from sample N / 2 on), the quotient formed in double and rounded once.
+ *    Delay: d = N samples.  A step that has received the samples below (k + 1) Bn emits y[k Bn - N + i], i < Bn, and 0 where
+ *    that index is negative: every frame that covers an emitted sample is complete.
+ *    strength == 0: the stage stays in the path with its delay and emits x[k Bn - N + i], the delayed input bit for bit.
+ *    Analysis, floor and the sums of the synthesis keep running, so the floor is learned when strength comes back.
+ *    On the device the transforms and the numerator are float32; the host twin transforms and synthesises in double and rounds
+ *    D, and y, once, and applies the float32 roundings of A2, F, S, l and m as defined.
+ *    The result depends on the samples received alone: the block length (shorter than H, so that a step completes no frame, or
+ *    longer than N), the other streams of a group and a repeated step change no bit.
+ *
+ * State, per stream and side: the last N samples, the N overlap-add sums behind the last sample emitted, the last nt rows of
+ * F, f (nb doubles); mu and sd once per side.  It is the session's own memory and exists twice: a step reads set cur and
+ * writes the other one whole, and the sets change places only when the step has succeeded (ring, carry, FIFOs, the board).
+ * Nothing in it is a stored position: the frames a step completes follow from the step counter x block.  One launch of one
+ * 256-lane workgroup per stream, per side and step; no atomics, no host synchronisation.
+ *
+ * Errors: a value out of the ranges below or not finite, a rate that is not the side's (or 0) or out of range, channels other
+ * than 0 or 1, mode 0 without a clip, a clip in mode 1 or of a length out of range return -1 with a message and write or
+ * open nothing. */
+typedef struct {
+  int32_t sample_rate, channels; /* 0 or the rate of the side; 0 or 1 */
+  int32_t mode;                 /* 0 profile, 1 adaptive (default 1) */
+  float strength;               /* 0 .. 1 (0.9; stage 15's 0.7 leaves the pauses 10 dB down, 0.9 gives 18 dB) */
+  float n_std;                  /* mode 0: 0 .. 10 (3) */
+  float knee_db;                /* mode 0: 0.1 .. 20 (1) */
+  float thresh_mult;            /* mode 1: 0 .. 20 (1) */
+  float slope;                  /* mode 1: 0.1 .. 100 (5) */
+  float time_constant_s;        /* mode 1, rising: 0.05 .. 30 (2) */
+  float fall_time_s;            /* mode 1, falling: 0.01 .. time_constant_s (0.2) */
+  float freq_smooth_hz;         /* >= 0 (500) */
+  float time_smooth_ms;         /* >= 0 (50) */
+} rvcx_live_denoise_params;
+/* one side of a session: params == NULL, the side is absent.  noise_hd: the clip of mode 0 (host or device), n_noise samples */
+typedef struct {
+  const rvcx_live_denoise_params* params;
+  const float* noise_hd;
+  int64_t n_noise;
+} rvcx_stream_dn_side;
+typedef struct {
+  rvcx_stream_dn_side in;       /* behind the input resampler (or on the 16 kHz mono block), in front of the ring, at 16 kHz */
+  rvcx_stream_dn_side out;      /* behind the output resampler, in front of the board, mono, at the delivery rate */
+} rvcx_stream_dn;
+/* N of stage 16 at this rate: the delay a side adds, in samples of its rate; -1 for a refused rate (host only) */
+int rvcx_stream_denoise_delay(int sr);
+/* T(n), N and the half-widths nf, nt of the given widths at this rate, before any refusal of their size (host only) */
+int rvcx_stream_denoise_frames(int64_t n, int sr, float freq_smooth_hz, float time_smooth_ms, int64_t* T, int32_t* N, int32_t* nf,
+                               int32_t* nt);
+/* dn == NULL or both sides absent: rvcx_stream_open_fx, launch for launch and bit for bit.  Every refusal of both sides is made
+ * first, and nothing is opened.  pre_sola_hd, offsets and the native tap of rvcx_stream_last_taps stay in front of the output
+ * side; its in16k tap returns what entered the ring, behind the input side. */
+int rvcx_stream_open_dn(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_stream_io*, const rvcx_fx_params* fx,
+                        const rvcx_stream_dn* dn, const rvcx_params* p, const int32_t* sid, const float* pitch, int* stream_id);
+/* new values for side 0 (input) or 1 (output) from the next step on.  Geometry, delay and the state's layout are fixed at
+ * open: a time_smooth_ms that changes nt is refused, and so is mode 0 on a side opened without a clip.  All state is kept (the
+ * floor stays learned).  A refused value: -1, nothing changed.  Refused for a side that was absent at open. */
+int rvcx_stream_set_denoise(rvcx_ctx*, int stream_id, int side, const rvcx_live_denoise_params*);
+/* device ms of the two sides in the last step ({input, output}; 0 for an absent side).  rvcx_last_timing keeps nine slots: the
+ * input side is counted in the first interval ("F0"), the output side in the last ("SOLA + copies").  rvcx_stream_delays adds
+ * N of each present side to the delay it reports. */
+int rvcx_stream_last_dn_ms(rvcx_ctx*, int stream_id, float* ms2);
+/* a side without a session and without a model: S mono rows of `frames` samples (x_hd: S x frames) at rate sr, cut into blocks
+ * of block_frames 10 ms frames (frames must be a multiple of block_frames * sr / 100), through the same state and kernel code
+ * a session runs per step; y_hd receives S x frames, delayed by N.  noise_hd / n_noise: the clip of mode 0, shared by the rows.
+ * Optional taps for the T(frames) frames completed: S_hd and m_hd (S, T, nb) float32, f_hd (S, T, nb) doubles (mode 1) */
+int rvcx_op_stream_denoise(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int sr, int block_frames,
+                           const rvcx_live_denoise_params*, const float* noise_hd, int64_t n_noise, float* y_hd, float* S_hd,
+                           double* f_hd, float* m_hd);
+/* host only, no context: stage 16 on the whole signal x[0 .. n) -> y (n samples, delayed by N).  Optional taps for the T(n)
+ * frames: D (T, nb, 2) float32, S and m (T, nb), f (T, nb) doubles (mode 1) */
+int rvcx_fx_denoise_live_host(const float* x, int64_t n, int sr, const float* noise, int64_t n_noise,
+                              const rvcx_live_denoise_params*, float* y, float* D, float* S, double* f, float* m);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
  * {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} -- a session's input resampler is counted in the
- * F0 interval, its output resampler in "SOLA + copies"; of the last rvcx_fx_chain: {high-pass, compressor, gate, reverb, low
+ * F0 interval, its output resampler in "SOLA + copies", and so are the input and the output side of stage 16; of the last
+ * rvcx_fx_chain: {high-pass, compressor, gate, reverb, low
  * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups); of the last rvcx_fx_loudness: {copies +
  * layout, chunk states, carry, K-weighting + energy, hop sums + gates, true peak, copies back, 0, total}; of the last
  * rvcx_fx_master: {stem loudness, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters, copies +

@@ -178,6 +178,8 @@ SYMBOLS = [
     "rvcx_fx_stretch_own_host", "rvcx_fx_stretch_override",
     "rvcx_fx_denoise_frames", "rvcx_fx_denoise_tiles", "rvcx_fx_denoise", "rvcx_op_fx_denoise_taps", "rvcx_fx_denoise_host",
     "rvcx_fx_denoise_smooth_host",
+    "rvcx_stream_denoise_delay", "rvcx_stream_denoise_frames", "rvcx_stream_open_dn", "rvcx_stream_set_denoise",
+    "rvcx_stream_last_dn_ms", "rvcx_op_stream_denoise", "rvcx_fx_denoise_live_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -308,6 +310,13 @@ def lib() -> C.CDLL:
         _lib.rvcx_op_fx_denoise_taps.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.rvcx_fx_denoise_host.argtypes = [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.rvcx_fx_denoise_smooth_host.argtypes = [vp, i64, i, i, i, vp]
+        _lib.rvcx_stream_denoise_delay.argtypes = [i]
+        _lib.rvcx_stream_denoise_frames.argtypes = [i64, i, f, f, vp, vp, vp, vp]
+        _lib.rvcx_stream_open_dn.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_stream_set_denoise.argtypes = [vp, i, i, vp]
+        _lib.rvcx_stream_last_dn_ms.argtypes = [vp, i, vp]
+        _lib.rvcx_op_stream_denoise.argtypes = [vp, vp, i, i64, i, i, vp, vp, i64, vp, vp, vp, vp]
+        _lib.rvcx_fx_denoise_live_host.argtypes = [vp, i64, i, vp, i64, vp, vp, vp, vp, vp, vp]
     return _lib
 
 
@@ -690,6 +699,99 @@ def fx_denoise_smooth_host(A2, nf, nt):
     return S
 
 
+# ---- live noise reduction on the host (rvcx.h stage 16) ---------------------------------------------------------------------------
+class LiveDenoiseParams(C.Structure):
+    """rvcx_live_denoise_params; make() fills the defaults of include/rvcx.h stage 16"""
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("mode", C.c_int32), ("strength", C.c_float),
+                ("n_std", C.c_float), ("knee_db", C.c_float), ("thresh_mult", C.c_float), ("slope", C.c_float),
+                ("time_constant_s", C.c_float), ("fall_time_s", C.c_float), ("freq_smooth_hz", C.c_float),
+                ("time_smooth_ms", C.c_float)]
+    DEFAULTS = dict(mode=1, strength=0.9, n_std=3.0, knee_db=1.0, thresh_mult=1.0, slope=5.0, time_constant_s=2.0,
+                    fall_time_s=0.2, freq_smooth_hz=500.0, time_smooth_ms=50.0)
+    MODES = {"profile": 0, "adaptive": 1}
+
+    @classmethod
+    def make(cls, sr=0, **values):
+        unknown = set(values) - set(cls.DEFAULTS)
+        if unknown:
+            raise RvcxError(f"LiveDenoiseParams: unknown value(s) {sorted(unknown)}")
+        v = dict(cls.DEFAULTS, **values)
+        v["mode"] = cls.MODES.get(v["mode"], v["mode"])
+        return cls(int(sr), 1, int(v["mode"]), *[float(v[k]) for k in list(cls.DEFAULTS)[1:]])
+
+    def values(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+
+class StreamDenoiseSide(C.Structure):
+    """rvcx_stream_dn_side: params NULL, the side is absent"""
+    _fields_ = [("params", C.c_void_p), ("noise", C.c_void_p), ("n_noise", C.c_int64)]
+
+
+class StreamDenoise(C.Structure):
+    """rvcx_stream_dn (`in` is `inp` here)"""
+    _fields_ = [("inp", StreamDenoiseSide), ("out", StreamDenoiseSide)]
+
+
+def _live_denoise(params, sr=0):
+    """(LiveDenoiseParams, noise clip or None) from a LiveDenoiseParams or a dict of values with an optional noise= array"""
+    if isinstance(params, LiveDenoiseParams):
+        return LiveDenoiseParams(int(sr), 1, *[getattr(params, k) for k in LiveDenoiseParams.DEFAULTS]), None
+    v = dict(params or {})
+    noise = v.pop("noise", None)
+    if noise is not None:
+        noise = f32(noise)
+        if noise.ndim != 1:
+            raise RvcxError("live denoise: the noise clip must be one channel of shape (samples,)")
+    return LiveDenoiseParams.make(sr, **v), noise
+
+
+def stream_denoise_delay(sr: int) -> int:
+    """N of stage 16 at this rate: the samples a side delays its signal by (RvcxError for a refused rate)"""
+    N = int(lib().rvcx_stream_denoise_delay(int(sr)))
+    if N < 0:
+        raise RvcxError("stream_denoise_delay: the sample rate must be a multiple of 100 Hz within 3200 .. 192000")
+    return N
+
+
+def stream_denoise_frames(n: int, sr: int, freq_smooth_hz=500.0, time_smooth_ms=50.0):
+    """(T frames complete in n samples, N, nf, nt) of stage 16"""
+    T, N, nf, nt = C.c_int64(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    _fx_host("stream_denoise_frames", lib().rvcx_stream_denoise_frames(int(n), int(sr), float(freq_smooth_hz), float(time_smooth_ms),
+                                                                       C.byref(T), C.byref(N), C.byref(nf), C.byref(nt)))
+    return int(T.value), int(N.value), int(nf.value), int(nt.value)
+
+
+def _live_taps(S, n, sr, mode, want, host):
+    if not want:
+        return {}
+    T, N, _, _ = stream_denoise_frames(n, sr)
+    shape = (T, N // 2 + 1) if S is None else (S, T, N // 2 + 1)
+    t = dict(S=np.zeros(shape, np.float32), m=np.zeros(shape, np.float32))
+    if host:
+        t.update(D=np.zeros(shape + (2,), np.float32))
+    if mode == 1:
+        t.update(f=np.zeros(shape, np.float64))
+    return t
+
+
+def fx_denoise_live_host(x, sr, params=None, noise=None, taps=False):
+    """stage 16 on the host (transforms and synthesis in double) on the whole signal -> y delayed by N, or (y, dict of the
+    taps D (T, nb, 2), S, m (T, nb) and f (T, nb), mode 1)"""
+    x = f32(x)
+    if x.ndim != 1:
+        raise RvcxError("fx_denoise_live_host: one channel of shape (samples,) expected")
+    p, z = _live_denoise(params, sr)
+    z = z if noise is None else f32(noise)
+    y = np.zeros_like(x)
+    rate_ok = lib().rvcx_stream_denoise_delay(int(sr)) > 0          # (a refused rate: the library says so below)
+    t = _live_taps(None, x.shape[0], sr, p.mode, taps, True) if rate_ok else {}
+    _fx_host("fx_denoise_live_host", lib().rvcx_fx_denoise_live_host(
+        x.ctypes.data, x.shape[0], int(sr), None if z is None else z.ctypes.data, 0 if z is None else z.shape[0], C.byref(p),
+        y.ctypes.data, *[t[k].ctypes.data if k in t else None for k in ("D", "S", "f", "m")]))
+    return (y, t) if taps else y
+
+
 _device_info_cache = {}
 
 
@@ -869,6 +971,7 @@ class StreamSession:
         self.block_out = int(lib().rvcx_stream_out_len(ctx._h, sid))      # frames per block as step() returns them
         self.out_channels = int(lib().rvcx_stream_out_channels(ctx._h, sid))   # 2 when the effects board is on
         self.effects = None                                               # the eighteen values in force (a dict), or None
+        self.denoise = [None, None]                                       # per side (in, out): the values in force, or None
         self.noise_len = int(lib().rvcx_stream_noise_len(ctx._h, sid))
         self.frames = int(lib().rvcx_stream_frames(ctx._h, sid))          # T of the TextEncoder
         din, dout = C.c_int32(0), C.c_int32(0)
@@ -954,6 +1057,28 @@ class StreamSession:
         self._ctx._ck(lib().rvcx_stream_last_fx_ms(self._ctx._h, self.id, ms), "stream_last_fx_ms")
         names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "total"]
         return dict(zip(names, [float(v) for v in ms]))
+
+    SIDES = {"in": 0, "input": 0, 0: 0, "out": 1, "output": 1, 1: 1}
+
+    def set_denoise(self, side, **changes):
+        """rvcx_stream_set_denoise: new values for some of the ten LiveDenoiseParams names on side "in" or "out", applied from
+        the next step on; the others keep their current value.  All state is kept (the floor stays learned).  A refused value
+        changes nothing; a side that was absent at open refuses the call."""
+        if side not in self.SIDES:
+            raise RvcxError("StreamSession.set_denoise: side must be 'in' or 'out'")
+        k = self.SIDES[side]
+        if self.denoise[k] is None:
+            raise RvcxError("StreamSession.set_denoise: the session was opened without noise reduction on this side (its "
+                            "delay is fixed at open)")
+        p = LiveDenoiseParams.make(0, **dict(self.denoise[k], **changes))
+        self._ctx._ck(lib().rvcx_stream_set_denoise(self._ctx._h, self.id, k, C.byref(p)), "stream_set_denoise")
+        self.denoise[k] = p.values()
+
+    def last_dn_ms(self):
+        """device ms of the input and the output noise gate in the last step (rvcx_stream_last_dn_ms; 0 for an absent side)"""
+        ms = (C.c_float * 2)()
+        self._ctx._ck(lib().rvcx_stream_last_dn_ms(self._ctx._h, self.id, ms), "stream_last_dn_ms")
+        return float(ms[0]), float(ms[1])
 
     def reset(self):
         """zero ring, carry, the board's state and the step counter: the session then replays a fresh one"""
@@ -1361,12 +1486,16 @@ class Context:
         return y
 
     def stream_open(self, model_id, params: "Params", sids, pitches, block_frames, context_frames, crossfade_frames,
-                    search_frames, in_rate=0, in_channels=1, out_rate=0, effects=None) -> "StreamSession":
+                    search_frames, in_rate=0, in_channels=1, out_rate=0, effects=None, denoise_in=None,
+                    denoise_out=None) -> "StreamSession":
         """rvcx_stream_open_io: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms).  in_rate /
         in_channels: what step() takes (0 or 16000 with one channel: 16 kHz mono); out_rate: what it returns (0 or the
         model's rate: the model's rate).  effects: a dict of add_effects names laid over FX_UI_DEFAULTS, or an FxParams --
-        the board runs inside every step on what would have left and step() returns stereo (rvcx_stream_open_fx).  With the
-        defaults this is rvcx_stream_open."""
+        the board runs inside every step on what would have left and step() returns stereo (rvcx_stream_open_fx).
+        denoise_in / denoise_out: a dict of LiveDenoiseParams values (with noise= a clip for mode 0), or a LiveDenoiseParams --
+        live noise reduction on the 16 kHz block in front of the ring / on what leaves, in front of the board; each side
+        delays its signal by stream_denoise_delay(rate) samples (rvcx_stream_open_dn).  With the defaults this is
+        rvcx_stream_open."""
         values = None if effects is None else fx_values(effects)
         sid, pit = i32(np.atleast_1d(sids)), f32(np.atleast_1d(pitches))
         if sid.ndim != 1 or sid.shape != pit.shape or sid.shape[0] < 1:
@@ -1374,6 +1503,23 @@ class Context:
         cfg = StreamCfg(int(sid.shape[0]), int(block_frames), int(context_frames), int(crossfade_frames), int(search_frames))
         io = StreamIO(int(in_rate), int(in_channels), int(out_rate), 0)
         h = C.c_int(0)
+        if denoise_in is not None or denoise_out is not None:
+            # stage 16 on the 16 kHz block in front of the ring and / or on what leaves, in front of the board
+            sides = [None if v is None else _live_denoise(v) for v in (denoise_in, denoise_out)]
+            dn = StreamDenoise()
+            for name, sd in zip(("inp", "out"), sides):
+                if sd is not None:
+                    p, z = sd
+                    setattr(dn, name, StreamDenoiseSide(C.cast(C.pointer(p), C.c_void_p), None if z is None else z.ctypes.data,
+                                                        0 if z is None else z.shape[0]))
+            fx = None if values is None else FxParams.make(values, 0, 0)
+            self._ck(lib().rvcx_stream_open_dn(self._h, int(model_id), C.byref(cfg), C.byref(io),
+                                               None if fx is None else C.byref(fx), C.byref(dn), C.byref(params),
+                                               sid.ctypes.data, pit.ctypes.data, C.byref(h)), "stream_open")
+            se = StreamSession(self, int(h.value), cfg, io, self.synth_upp(model_id))
+            se.effects = values
+            se.denoise = [None if sd is None else sd[0].values() for sd in sides]
+            return se
         if values is None:
             self._ck(lib().rvcx_stream_open_io(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(params),
                                                _p(sid, C.c_int32), _p(pit), C.byref(h)), "stream_open")
@@ -1400,6 +1546,35 @@ class Context:
         self._ck(lib().rvcx_op_stream_fx(self._h, x.ctypes.data, S, C.c_int64(frames), ch, int(sr), int(block_frames),
                                          C.byref(fx), mask, y.ctypes.data), "op_stream_fx")
         return y
+
+    def stream_denoise(self, x, sr: int, block_frames: int, params=None, noise=None, taps=False):
+        """rvcx_op_stream_denoise: a session's noise gate without a session.  x (S, frames) float32 at rate sr, cut into blocks
+        of block_frames * sr / 100 samples and sent through the state and kernel a session runs per step -> (S, frames),
+        delayed by stream_denoise_delay(sr).  params: a dict of LiveDenoiseParams values or a LiveDenoiseParams; noise: the
+        clip of mode 0 (a numpy array, or an int device pointer with its length as a pair).  taps=True: (y, dict of S, m
+        (S, T, nb) and f (mode 1))."""
+        x = f32(x)
+        if x.ndim != 2:
+            raise RvcxError("stream_denoise: x must be (S, frames)")
+        S, frames = x.shape
+        p, z = _live_denoise(params, sr)
+        zp, zn = None, 0
+        if isinstance(noise, tuple):
+            zp, zn = int(noise[0]), int(noise[1])
+        else:
+            z = z if noise is None else f32(noise)
+            if z is not None:
+                if z.ndim != 1:
+                    raise RvcxError("stream_denoise: the noise clip must be one channel of shape (samples,)")
+                zp, zn = z.ctypes.data, z.shape[0]
+        y = np.full((S, frames), np.nan, np.float32)
+        rate_ok = lib().rvcx_stream_denoise_delay(int(sr)) > 0      # (a refused rate: the library says so below)
+        t = _live_taps(S, frames, sr, p.mode, taps, False) if rate_ok else {}
+        self._ck(lib().rvcx_op_stream_denoise(self._h, x.ctypes.data, S, C.c_int64(frames), int(sr), int(block_frames), C.byref(p),
+                                              zp, C.c_int64(zn), y.ctypes.data,
+                                              *[t[k].ctypes.data if k in t else None for k in ("S", "f", "m")]),
+                 "op_stream_denoise")
+        return (y, t) if taps else y
 
     def load_rmvpe(self, cfg_struct, state: dict):
         tbl, keep = make_table(state)

@@ -10,6 +10,7 @@
 #include <unordered_map>
 
 #include "ctx.h"
+#include "denoise_live.h"
 #include "effects.h"
 #include "layers.h"
 #include "models.h"
@@ -116,7 +117,27 @@ struct StreamSession {
   rvcx_fx_params fxp{};                    // the parameters in force
   float* fx_out = nullptr;                 // (S, block, 2): what the step copies out
   float fx_ms[8] = {0};                    // rvcx_stream_last_fx_ms
+  // live noise reduction (rvcx_stream_open_dn; rvcx.h stage 16): side 0 on the 16 kHz block in front of the ring, side 1 behind
+  // the output resampler in front of the board.  State sets as above; tables, profile and staging are the session's own
+  struct DnSide {
+    std::unique_ptr<DnLive> d;             // null: the side is absent
+    rvcx_live_denoise_params p{};          // the parameters in force
+    float* tables = nullptr;               // w (N floats), then the twiddles (N / 2 pairs)
+    double* prof = nullptr;                // mode 0 at open: mu, then sd (nb doubles each)
+    float* stage = nullptr;                // (S, B): side 0, the block as it came; side 1, what the side emits
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } dn[2];
+  float dn_ms[2] = {0, 0};                 // rvcx_stream_last_dn_ms
   ~StreamSession() {
+    for (DnSide& sd : dn) {
+      if (sd.d)
+        for (void* q : {(void*)sd.d->state[0], (void*)sd.d->state[1], (void*)sd.d->acc})
+          if (q) (void)hipFree(q);
+      for (void* q : {(void*)sd.tables, (void*)sd.prof, (void*)sd.stage})
+        if (q) (void)hipFree(q);
+      for (hipEvent_t e : sd.ev)
+        if (e) (void)hipEventDestroy(e);
+    }
     if (fx)
       for (void* q : {(void*)fx->state[0], (void*)fx->state[1], (void*)fx->work, (void*)fx_out})
         if (q) (void)hipFree(q);

@@ -202,15 +202,23 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
     // (1) the rings move left by one block; a session with an input side first brings the caller's blocks to 16 kHz mono
     // (FIFO set cur -> the other one, like everything below that is state)
     float* blocks = se.blocks[se.cur ^ 1];
+    StreamSession::DnSide& dn_in = se.dn[0];
+    StreamSession::DnSide& dn_out = se.dn[1];
+    float* raw = dn_in.d ? dn_in.stage : blocks;      // a session with an input noise gate: the 16 kHz block as it came
     if (se.in.on) {
       const size_t row = (size_t)se.in.g.B_in * se.in.g.channels;
       for (int s = 0; s < S; ++s)
         RVCX_HIP(hipMemcpyAsync(se.stage + (size_t)s * row, block16k[s], row * 4, hipMemcpyDefault, st));
-      launch_stream_resample(se.in.g, se.in.f, se.in.fifo[se.cur], se.in.fifo[se.cur ^ 1], se.stage, (long)row, blocks, blk, S,
+      launch_stream_resample(se.in.g, se.in.f, se.in.fifo[se.cur], se.in.fifo[se.cur ^ 1], se.stage, (long)row, raw, blk, S,
                              se.step, st);
     } else {
       for (int s = 0; s < S; ++s)
-        RVCX_HIP(hipMemcpyAsync(blocks + (size_t)s * blk, block16k[s], (size_t)blk * 4, hipMemcpyDefault, st));
+        RVCX_HIP(hipMemcpyAsync(raw + (size_t)s * blk, block16k[s], (size_t)blk * 4, hipMemcpyDefault, st));
+    }
+    if (dn_in.d) {                                    // stage 16 in front of the ring, from the state it carries
+      RVCX_HIP(hipEventRecord(dn_in.ev[0], st));
+      dn_live_step(*dn_in.d, raw, blk, se.cur, se.step, blocks, blk, st);
+      RVCX_HIP(hipEventRecord(dn_in.ev[1], st));
     }
     const float* ring_old = se.ring[se.cur];
     float* ring = se.ring[se.cur ^ 1];
@@ -277,6 +285,13 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
       launch_stream_resample(se.out.g, se.out.f, se.out.fifo[se.cur], se.out.fifo[se.cur ^ 1], dout, Lb, r, Bout, S, se.step, st);
       dres = r, Lo = Bout;
     }
+    // (6b) a session with an output noise gate: stage 16 on what would have left, in front of the board
+    if (dn_out.d) {
+      RVCX_HIP(hipEventRecord(dn_out.ev[0], st));
+      dn_live_step(*dn_out.d, dres, Lo, se.cur, se.step, dn_out.stage, Lo, st);
+      RVCX_HIP(hipEventRecord(dn_out.ev[1], st));
+      dres = dn_out.stage;
+    }
     // (7) a session with effects: the board on what would have left, from the state it carries; stereo leaves
     if (se.fx) {
       fx_live_step(*se.fx, dres, Lo, 1, se.cur, se.step, se.fx_out, 2 * Lo, st, ev + 8);
@@ -300,6 +315,8 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
         for (int k = 0; k < 7; ++k) RVCX_HIP(hipEventElapsedTime(&se.fx_ms[k], ev[8 + k], ev[9 + k]));
         RVCX_HIP(hipEventElapsedTime(&se.fx_ms[7], ev[8], ev[15]));
       }
+      for (int k = 0; k < 2; ++k)
+        if (se.dn[k].d) RVCX_HIP(hipEventElapsedTime(&se.dn_ms[k], se.dn[k].ev[0], se.dn[k].ev[1]));
     }
     A.reset();
     done = &se;
@@ -322,6 +339,9 @@ int rvcx_stream_reset(rvcx_ctx* ctx, int stream_id) {
     if (sd->fifo[se.cur]) RVCX_HIP(hipMemsetAsync(sd->fifo[se.cur], 0, (size_t)se.S * sd->g.L * sizeof(double), C->stream));
   if (se.fx)        // a ring of the board is complete only over both sets
     for (float* q : se.fx->state) RVCX_HIP(hipMemsetAsync(q, 0, (size_t)se.S * se.fx->L.per_stream * 4, C->stream));
+  for (StreamSession::DnSide& sd : se.dn)
+    if (sd.d)
+      for (float* q : sd.d->state) RVCX_HIP(hipMemsetAsync(q, 0, (size_t)se.S * sd.d->per_stream * 4, C->stream));
   RVCX_HIP(hipStreamSynchronize(C->stream));
   se.step = 0;
   API_END
@@ -358,8 +378,8 @@ int rvcx_stream_delays(rvcx_ctx* ctx, int stream_id, int32_t* in_delay_16k, int3
   auto it = ctx->sessions.find(stream_id);
   if (it == ctx->sessions.end()) return -1;
   const StreamSession& se = *it->second;
-  if (in_delay_16k) *in_delay_16k = se.in.on ? se.in.g.delay : 0;
-  if (out_delay) *out_delay = se.out.on ? se.out.g.delay : 0;
+  if (in_delay_16k) *in_delay_16k = (se.in.on ? se.in.g.delay : 0) + (se.dn[0].d ? se.dn[0].d->g.N : 0);
+  if (out_delay) *out_delay = (se.out.on ? se.out.g.delay : 0) + (se.dn[1].d ? se.dn[1].d->g.N : 0);
   return 0;
 }
 

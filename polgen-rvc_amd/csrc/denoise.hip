@@ -26,6 +26,7 @@
 // A2, S, l, m and g are defined with every rounding written out
 #pragma clang fp contract(off)
 
+#include "denoise_device.h"   // the pointwise rules, one text for the kernels and the host twins
 #include "fft_device.h"
 
 namespace rvcx {
@@ -35,26 +36,6 @@ namespace {
 constexpr double kPi = 3.14159265358979323846;
 constexpr int kDenoiseAhead = 8;          // frames the floor kernel fetches at once
 static_assert(kDenoiseTileK == 64, "the smoothing kernel gives a lane to each bin of a tile row");
-
-// ---- the pointwise rules, one text for the kernels and the host twin --------------------------------------------------------------
-__host__ __device__ inline float dn_level(float s) { return 10.f * log10f(s + 1e-20f); }
-__host__ __device__ inline float dn_sigmoid(float z) { return 1.f / (1.f + expf(-z)); }
-__host__ __device__ inline float dn_mask0(float l, double mu, double sd, float n_std, float knee) {
-  const double thr = mu + (double)n_std * sd;
-  return dn_sigmoid((float)(((double)l - thr) / (double)knee));
-}
-__host__ __device__ inline float dn_mask1(double A, double b, float thresh_mult, float slope) {
-  const double r = (A - b) / (b + 1e-10);
-  return dn_sigmoid((float)((r - (double)thresh_mult) * (double)slope));
-}
-__host__ __device__ inline float dn_gain(float strength, float m) { return 1.f - strength * (1.f - m); }
-// the weights of the indices i + d, |d| <= h, that lie in 0 .. n - 1
-__host__ __device__ inline int dn_weight_sum(long i, long n, int h) {
-  const long lo = -(long)h > -i ? -(long)h : -i, hi = (long)h < n - 1 - i ? (long)h : n - 1 - i;
-  int s = 0;
-  for (long d = lo; d <= hi; ++d) s += h + 1 - (int)(d < 0 ? -d : d);
-  return s;
-}
 
 __device__ __forceinline__ long rows_T(const FxDenoiseRows& q, int r, int H) { return (long)q.len[r] / H + 1; }
 
