@@ -43,6 +43,16 @@ build/asan/librvcx_asan.so: $(ASAN_OBJS) build/asan/hipstub.o build/asan/fatbins
 
 host-asan: build/asan/librvcx_asan.so
 
+# a stand-alone program (its own main, no Python, nothing preloaded) over the host twins of stages 17 and 18, linked against the
+# library above and run on the spot
+build/asan/formant_main: tools/formant_asan_main.cpp build/asan/librvcx_asan.so
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	    -shared-libasan -Iinclude $< -Lbuild/asan -lrvcx_asan -Wl,-rpath,'$$ORIGIN' \
+	    -Wl,-rpath,$(dir $(shell $(CLANGXX) -print-file-name=libclang_rt.asan-x86_64.so)) -o $@
+
+host-asan-formant: build/asan/formant_main
+	ASAN_OPTIONS=abort_on_error=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 build/asan/formant_main
+
 # ---- the same host pass under ThreadSanitizer (tools/host_tsan.sh runs tools/host_tickets_driver.py on it): conversion
 # tickets are the first code of the library where the state of two requests can meet
 TSAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -Wno-pass-failed -Wno-unused-result -fsanitize=thread \

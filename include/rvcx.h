@@ -954,6 +954,77 @@ int rvcx_op_stream_denoise(rvcx_ctx*, const float* x_hd, int S, int64_t frames, 
 int rvcx_fx_denoise_live_host(const float* x, int64_t n, int sr, const float* noise, int64_t n_noise,
                               const rvcx_live_denoise_params*, float* y, float* D, float* S, double* f, float* m);
 
+/* ---- formant shift and formant-preserving pitch shift ------------------------------------------------------------------
+ * Stages 17 and 18 continue "post-production" (signal, rates, error rules): the timbre control.  Per frame a spectral envelope
+ * is estimated (the "true envelope": cepstral smoothing iterated under the maximum with the log spectrum, so that it rides the
+ * harmonic peaks) and replaced by a warped copy of an envelope: the frame's own, warped in frequency (a formant shift), or the
+ * envelope of a second signal at the same frame (stage 18: the untransposed signal's, which keeps the formants of a vocal in
+ * place through a key change).  Maximum, linear warp and clamp are continuous in the spectrum: nothing flips a bin between
+ * float32 and float64.  The definition is this project's own; tested against float64 (tests/formant_reference.py).
+ *
+ * 17 envelope transfer, per channel.  N, H = N / 4, nb = N / 2 + 1 and w are stage 13's.  Frames t = 0 .. T - 1, T = floor(n / H)
+ *    + 1; D[t][k] as in stage 13 (float32 pairs); A2[k] = fl(fl(re re) + fl(im im)), no fma.
+ *    Log spectrum: top = max_k A2[k] (exact), eps = fl(fl(1e-10f top) + 1e-20f), L[k] = fl(0.5f logf(fl(A2[k] + eps))).
+ *    True envelope: nc = floor(quefrency_ms sr / 1000) formed in double, 1 <= nc <= N / 8.  lift(V): the length-N real even
+ *    extension of V[0 .. nb) (V[N - k] = V[k]), its inverse transform c[q] (real, even), c[q] kept for q <= nc, c[N - q] = c[q]
+ *    set from it, the rest zero; the forward transform, its real part on 0 .. nb - 1.  V_0 = L; for i = 0 .. iterations: E =
+ *    lift(V_i), V_{i+1} = max(L, E): iterations + 1 lifts.  E is float32 after every lift.
+ *    Target: Es = the item's own E, or, with a source (a second signal of the same rate, channel count and length n, channel c
+ *    serving channel c), the E of frame t of the source through the same steps.  Warp, in double: u = k / ratio, i = floor(u),
+ *    f = u - i, W[k] = (float)((1 - f) Es[i] + f Es[i + 1]), W[k] = Es[nb - 1] when i >= nb - 1.
+ *    Gain: d = amount (W[k] - E[k]) in double, clamped to +- max_gain_db ln(10) / 20, g = expf((float) d).
+ *    Energy (keep_energy == 1): e0 = sum_k c_k A2[k], e1 = sum_k c_k ((g g) A2[k]), c_k = 1 at k = 0 and k = nb - 1, else 2, in
+ *    double, every product rounded: 256 partial sums, partial p over the bins k = p mod 256 in ascending k, then the partials
+ *    added in ascending p.  s = (float) sqrt(e0 / e1), 1 when e1 == 0; s = 1 with keep_energy == 0.
+ *    Synthesis is stage 15's: Y = fl(g s) D (the imaginary parts of bins 0 and N / 2 dropped), fr_t = w irfft(Y_t) (scaling
+ *    1 / N), y[i] = sum_t fr_t[i + N / 2 - t H] / sum_t w^2[i + N / 2 - t H] over the frames that cover i in ascending t, the
+ *    divisor in double; 0 where the divisor is <= 1e-8.  The output has n frames.
+ *    On the device the transforms (those of the lifts too), E and the numerator are float32; the envelope of the frame and of
+ *    its source frame pass through the lifts as the real and the imaginary part of one complex sequence.  The host twin
+ *    transforms and synthesises in double and rounds D, E (after every lift), W, g, s and y as defined.  Given the same A2
+ *    and g, s is equal on both sides bit for bit.
+ *    Skip: amount == 0 launches nothing; an item without a source at ratio == 1 is its own target and is not run.  In both cases
+ *    the output is the input bit for bit.
+ *    A result depends on the item and its source alone: B, the grouping, RVCX_MAX_BATCH and the other members change no bit.
+ * 18 formant-preserving pitch shift by s semitones: stage 14, then stage 17 on its output with src = the stage's own input and
+ *    ratio = 1 (both have n frames on one grid).  P == sr: everything is skipped, the output is the input bit for bit.
+ *
+ * Errors: a value out of the ranges below or not finite, a rate or channel count out of range, nc outside 1 .. N / 8, n < 1
+ * return -1 with a message and write nothing.  An item that does not fit the arena budget on its own is refused with a
+ * message that names its size (one item is not cut into segments).  A source has its item's length by definition: the ABI
+ * takes no second length, the Python layer refuses a source of another length. */
+typedef struct {
+  int32_t sample_rate, channels;
+  float ratio;                  /* 0.5 .. 2 (1): formants move up by this factor */
+  float amount;                 /* 0 .. 1 (1) */
+  float quefrency_ms;           /* > 0 with 1 <= nc <= N / 8 (1.5) */
+  int32_t iterations;           /* 0 .. 16 (8) */
+  float max_gain_db;            /* 0 .. 48 (24) */
+  int32_t keep_energy;          /* 0 or 1 (1) */
+} rvcx_fx_formant_params;
+/* T, N and nc of an item of n frames at this rate and quefrency (host only) */
+int rvcx_fx_formant_frames(int64_t n, int sr, float quefrency_ms, int64_t* T, int32_t* N, int32_t* nc);
+/* stage 17 on B items of params->channels channels: y_hd[b] receives (n[b], channels).  src_hd may be NULL, and so may any
+ * entry of it; src_hd[b] holds (n[b], channels).  Groups as rvcx_fx_chain. */
+int rvcx_fx_formant(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, const float* const* src_hd,
+                    const rvcx_fx_formant_params*, float* const* y_hd);
+/* stage 18 on B items: y_hd[b] receives (n[b], channels); no output may overlap any input of the call, in whole or in part
+ * (refused: stage 14 writes the outputs while the inputs are still the sources).  params may be NULL (the defaults);
+ * its sample_rate, channels and ratio are not read. */
+int rvcx_fx_pitch_shift_formant(rvcx_ctx*, int B, const float* const* x_hd, const int64_t* n, int channels, int sr,
+                                double semitones, const rvcx_fx_formant_params*, float* const* y_hd);
+/* stage 17 on one channel of one item with its intermediates (each optional): D_hd (T, nb, 2) float32, E_hd, Es_hd and g_hd
+ * (T, nb), s_hd (T) */
+int rvcx_op_fx_formant_taps(rvcx_ctx*, const float* x_hd, int64_t n, const float* src_hd, const rvcx_fx_formant_params*,
+                            float* y_hd, float* D_hd, float* E_hd, float* Es_hd, float* g_hd, float* s_hd);
+/* Host only, no context, no GPU.  The taps (optional) as above and for one channel only.  rvcx_fx_formant_envelope_host: E of
+ * one frame from its nb = N / 2 + 1 values L */
+int rvcx_fx_formant_host(const float* x, int64_t n, const float* src, const rvcx_fx_formant_params*, float* y, float* D,
+                         float* E, float* Es, float* g, float* s);
+int rvcx_fx_pitch_shift_formant_host(const float* x, int64_t n, int channels, int sr, double semitones,
+                                     const rvcx_fx_formant_params*, float* y);
+int rvcx_fx_formant_envelope_host(const float* L, int N, int nc, int iterations, float* E);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
@@ -966,7 +1037,9 @@ int rvcx_fx_denoise_live_host(const float* x, int64_t n, int sr, const float* no
  * layout, total}; of the last rvcx_fx_stretch / rvcx_fx_pitch_shift: {copies + layout, transforms, owners, scan, inverse
  * transforms, overlap-add, resampler, layout + copies back, total} (all zero when stage 14 was skipped); of the last
  * rvcx_fx_denoise: {copies in + layout, analysis, smoothing, statistics (mode 0) or floor + mask (mode 1), mask (mode 0),
- * synthesis, overlap-add, copies back, total} (all zero when stage 15 was skipped) */
+ * synthesis, overlap-add, copies back, total} (all zero when stage 15 was skipped); of the last rvcx_fx_formant /
+ * rvcx_fx_pitch_shift_formant: {copies in + layout, frames, overlap-add, copies back, 0, 0, 0, stage 14 (stage 18 only), total}
+ * (all zero when everything was skipped) */
 int rvcx_last_timing(rvcx_ctx*, float* ms9);
 /* HIP-event profile of the MFMA conv kernel family: begin=1 starts recording an event pair around
  * every conv launch on the library stream; begin=0 stops and returns, per tile configuration

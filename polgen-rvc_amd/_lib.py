@@ -180,6 +180,8 @@ SYMBOLS = [
     "rvcx_fx_denoise_smooth_host",
     "rvcx_stream_denoise_delay", "rvcx_stream_denoise_frames", "rvcx_stream_open_dn", "rvcx_stream_set_denoise",
     "rvcx_stream_last_dn_ms", "rvcx_op_stream_denoise", "rvcx_fx_denoise_live_host",
+    "rvcx_fx_formant_frames", "rvcx_fx_formant", "rvcx_fx_pitch_shift_formant", "rvcx_op_fx_formant_taps",
+    "rvcx_fx_formant_host", "rvcx_fx_pitch_shift_formant_host", "rvcx_fx_formant_envelope_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -317,6 +319,13 @@ def lib() -> C.CDLL:
         _lib.rvcx_stream_last_dn_ms.argtypes = [vp, i, vp]
         _lib.rvcx_op_stream_denoise.argtypes = [vp, vp, i, i64, i, i, vp, vp, i64, vp, vp, vp, vp]
         _lib.rvcx_fx_denoise_live_host.argtypes = [vp, i64, i, vp, i64, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_formant_frames.argtypes = [i64, i, f, vp, vp, vp]
+        _lib.rvcx_fx_formant.argtypes = [vp, i, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_pitch_shift_formant.argtypes = [vp, i, vp, vp, i, i, d, vp, vp]
+        _lib.rvcx_op_fx_formant_taps.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_formant_host.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_pitch_shift_formant_host.argtypes = [vp, i64, i, i, d, vp, vp]
+        _lib.rvcx_fx_formant_envelope_host.argtypes = [vp, i, i, i, vp]
     return _lib
 
 
@@ -697,6 +706,125 @@ def fx_denoise_smooth_host(A2, nf, nt):
     _fx_host("fx_denoise_smooth_host", lib().rvcx_fx_denoise_smooth_host(A2.ctypes.data, A2.shape[0], A2.shape[1], int(nf), int(nt),
                                                                          S.ctypes.data))
     return S
+
+
+# ---- formant shift and formant-preserving pitch shift on the host (rvcx.h stages 17 and 18) ------------------------------------
+class FxFormantParams(C.Structure):
+    """rvcx_fx_formant_params; make() fills the defaults of include/rvcx.h stage 17 (semitones= sets ratio = 2^(s / 12))"""
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("ratio", C.c_float), ("amount", C.c_float),
+                ("quefrency_ms", C.c_float), ("iterations", C.c_int32), ("max_gain_db", C.c_float), ("keep_energy", C.c_int32)]
+    DEFAULTS = dict(ratio=1.0, amount=1.0, quefrency_ms=1.5, iterations=8, max_gain_db=24.0, keep_energy=1)
+    INTS = ("iterations", "keep_energy")
+
+    @classmethod
+    def make(cls, sr, channels=1, **values):
+        if "semitones" in values:
+            if "ratio" in values:
+                raise RvcxError("FxFormantParams: ratio or semitones, not both")
+            values["ratio"] = formant_ratio(values.pop("semitones"))
+        unknown = set(values) - set(cls.DEFAULTS)
+        if unknown:
+            raise RvcxError(f"FxFormantParams: unknown value(s) {sorted(unknown)}")
+        v = dict(cls.DEFAULTS, **values)
+        for k in cls.INTS:
+            if int(v[k]) != v[k]:
+                raise RvcxError(f"FxFormantParams: {k} must be an integer")
+        return cls(int(sr), int(channels), *[(int if k in cls.INTS else float)(v[k]) for k in cls.DEFAULTS])
+
+    def with_shape(self, sr, channels):
+        return type(self)(int(sr), int(channels), *[getattr(self, k) for k in self.DEFAULTS])
+
+
+def formant_ratio(semitones) -> float:
+    """ratio of stage 17 for a move of the formants by `semitones`: 2^(s / 12), |s| <= 12"""
+    s = float(semitones)
+    if not np.isfinite(s) or abs(s) > 12.0:
+        raise RvcxError("formant_ratio: semitones must lie in -12 .. 12")
+    return float(np.float32(2.0 ** (s / 12.0)))
+
+
+def formant_shift_params(sr, channels, semitones, quefrency_ms=1.5, amount=1.0):
+    """the FxFormantParams of a formant shift by `semitones` as the mirror modules build them, or None at 0 semitones; every
+    refusal (semitones, amount, the rate, a quefrency outside 1 <= nc <= N / 8) as ValueError, before anything is read or
+    written"""
+    if not (np.isfinite(semitones) and abs(semitones) <= 12.0):
+        raise ValueError(f"formant shift of {semitones!r} semitones: a finite value within -12 .. 12 is expected")
+    if not (np.isfinite(amount) and 0.0 <= amount <= 1.0):
+        raise ValueError(f"formant shift amount {amount!r}: a value within 0 .. 1 is expected")
+    if not (np.isfinite(quefrency_ms) and quefrency_ms > 0.0):
+        raise ValueError(f"formant quefrency of {quefrency_ms!r} ms: a positive value is expected")
+    try:
+        fx_formant_frames(1, sr, quefrency_ms)                      # the rate, and nc against N / 8
+    except RvcxError as e:
+        raise ValueError(str(e)) from None
+    if not semitones:
+        return None
+    return FxFormantParams.make(sr, channels, semitones=float(semitones), quefrency_ms=float(quefrency_ms), amount=float(amount))
+
+
+def fx_formant_frames(n: int, sr: int, quefrency_ms=1.5):
+    """(T frames, N, nc) of stage 17 for n frames at sr"""
+    T, N, nc = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    _fx_host("fx_formant_frames", lib().rvcx_fx_formant_frames(int(n), int(sr), float(quefrency_ms), C.byref(T), C.byref(N),
+                                                               C.byref(nc)))
+    return int(T.value), int(N.value), int(nc.value)
+
+
+def _formant_taps(n, params, want):
+    """arrays for the optional outputs of one channel: D, E, Es, g and s"""
+    if not want:
+        return {}
+    T, N, _ = fx_formant_frames(n, params.sample_rate, params.quefrency_ms)
+    nb = N // 2 + 1
+    return dict(D=np.zeros((T, nb, 2), np.float32), E=np.zeros((T, nb), np.float32), Es=np.zeros((T, nb), np.float32),
+                g=np.zeros((T, nb), np.float32), s=np.zeros(T, np.float32))
+
+
+def _formant_tap_ptrs(t):
+    return [t[k].ctypes.data if k in t else None for k in ("D", "E", "Es", "g", "s")]
+
+
+def _formant_source(source, x, what):
+    """a source as float32 of the item's shape, or None"""
+    if source is None:
+        return None
+    z, _ = _fx_sig(source, what)
+    if z.shape != x.shape:
+        raise RvcxError(f"{what}: the source has shape {z.shape}, the item {x.shape} (same length and channel count required)")
+    return z
+
+
+def fx_formant_host(x, sr, params=None, source=None, taps=False):
+    """stage 17 on the host (transforms and synthesis in double) -> y, or (y, dict of taps) for a one-channel signal"""
+    x, ch = _fx_sig(x, "fx_formant_host")
+    p = (params or FxFormantParams.make(sr, ch)).with_shape(sr, ch)
+    z = _formant_source(source, x, "fx_formant_host")
+    y = np.zeros_like(x)
+    t = _formant_taps(x.shape[0], p, taps)
+    _fx_host("fx_formant_host", lib().rvcx_fx_formant_host(x.ctypes.data, x.shape[0], None if z is None else z.ctypes.data,
+                                                           C.byref(p), y.ctypes.data, *_formant_tap_ptrs(t)))
+    return (y, t) if taps else y
+
+
+def fx_pitch_shift_formant_host(x, sr, semitones, params=None):
+    """stage 18 on the host -> y of x's shape"""
+    x, ch = _fx_sig(x, "fx_pitch_shift_formant_host")
+    p = (params or FxFormantParams.make(sr, ch)).with_shape(sr, ch)
+    y = np.zeros_like(x)
+    _fx_host("fx_pitch_shift_formant_host", lib().rvcx_fx_pitch_shift_formant_host(x.ctypes.data, x.shape[0], ch, int(sr),
+                                                                                   float(semitones), C.byref(p), y.ctypes.data))
+    return y
+
+
+def fx_formant_envelope_host(L, N, nc, iterations=8):
+    """the true envelope of one frame from its nb = N / 2 + 1 values L (float32)"""
+    L = np.ascontiguousarray(L, dtype=np.float32)
+    if L.shape != (int(N) // 2 + 1,):
+        raise RvcxError("fx_formant_envelope_host: N / 2 + 1 values expected")
+    E = np.zeros_like(L)
+    _fx_host("fx_formant_envelope_host", lib().rvcx_fx_formant_envelope_host(L.ctypes.data, int(N), int(nc), int(iterations),
+                                                                             E.ctypes.data))
+    return E
 
 
 # ---- live noise reduction on the host (rvcx.h stage 16) ---------------------------------------------------------------------------
@@ -2098,11 +2226,20 @@ class Context:
         self._ck(lib().rvcx_fx_stretch(self._h, B, xp, n, ch, int(sr), int(P), int(Q), yp), "fx_stretch")
         return [y[:fx_stretch_len(x.shape[0], P, Q)] for x, y in zip(xs, ys)]
 
-    def fx_pitch_shift(self, items, sr, semitones):
-        """rvcx_fx_pitch_shift: every item shifted by `semitones` at its own length"""
+    def fx_pitch_shift(self, items, sr, semitones, preserve_formants=False, formant_params=None):
+        """rvcx_fx_pitch_shift: every item shifted by `semitones` at its own length.  preserve_formants: stage 18
+        (rvcx_fx_pitch_shift_formant), the envelope of each item put back onto its shifted copy; formant_params: the
+        FxFormantParams of that transfer (its ratio is not read)"""
         xs, ch, B, xp, n = self._fx_items(items, "fx_pitch_shift")
         ys = [np.zeros_like(x) for x in xs]
         yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        if preserve_formants:
+            p = (formant_params or FxFormantParams.make(sr, ch)).with_shape(sr, ch)
+            self._ck(lib().rvcx_fx_pitch_shift_formant(self._h, B, xp, n, ch, int(sr), float(semitones), C.byref(p), yp),
+                     "fx_pitch_shift_formant")
+            return ys
+        if formant_params is not None:
+            raise RvcxError("fx_pitch_shift: formant_params without preserve_formants")
         self._ck(lib().rvcx_fx_pitch_shift(self._h, B, xp, n, ch, int(sr), float(semitones), yp), "fx_pitch_shift")
         return ys
 
@@ -2167,6 +2304,44 @@ class Context:
         lib().rvcx_last_timing(self._h, ms)
         names = ["copies_in", "analysis", "smoothing", "stats_or_floor", "mask", "synthesis", "overlap_add", "copies_out", "total"]
         return dict(zip(names, [float(v) for v in ms]))
+
+    # ---- formant shift (rvcx.h stages 17 and 18; stage 18 is fx_pitch_shift(preserve_formants=True)) --------------------------
+    def fx_formant(self, items, sr, params=None, source=None):
+        """rvcx_fx_formant: a list of float32 signals of one rate and channel count in one call -> list of arrays.  source:
+        a list with one entry (an array of its item's shape, or None) per item"""
+        xs, ch, B, xp, n = self._fx_items(items, "fx_formant")
+        p = (params or FxFormantParams.make(sr, ch)).with_shape(sr, ch)
+        if source is None:
+            srcs = [None] * B
+        else:
+            if isinstance(source, np.ndarray) or len(source) != B:
+                raise RvcxError("fx_formant: one source entry per item expected")
+            srcs = [_formant_source(z, x, "fx_formant") for z, x in zip(source, xs)]
+        ys = [np.zeros_like(x) for x in xs]
+        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        zp = (C.c_void_p * B)(*[None if z is None else z.ctypes.data for z in srcs])
+        self._ck(lib().rvcx_fx_formant(self._h, B, xp, n, zp, C.byref(p), yp), "fx_formant")
+        return ys
+
+    def fx_formant_taps(self, x, sr, params=None, source=None):
+        """rvcx_op_fx_formant_taps on one channel -> (y, dict of D (T, nb, 2), E, Es, g (T, nb) and s (T))"""
+        x, ch = self._fx_in(x)
+        if ch != 1 or x.ndim != 1:
+            raise RvcxError("fx_formant_taps: one channel of shape (frames,) expected")
+        p = (params or FxFormantParams.make(sr, 1)).with_shape(sr, 1)
+        z = _formant_source(source, x, "fx_formant_taps")
+        y = np.zeros_like(x)
+        t = _formant_taps(x.shape[0], p, True)
+        self._ck(lib().rvcx_op_fx_formant_taps(self._h, x.ctypes.data, x.shape[0], None if z is None else z.ctypes.data,
+                                               C.byref(p), y.ctypes.data, *_formant_tap_ptrs(t)), "op_fx_formant_taps")
+        return y, t
+
+    def fx_formant_timing(self):
+        """device ms of the last fx_formant / fx_pitch_shift(preserve_formants=True) call"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        names = ["copies_in", "frames", "overlap_add", "copies_out", "_4", "_5", "_6", "pitch_shift", "total"]
+        return {k: float(v) for k, v in zip(names, ms) if not k.startswith("_")}
 
     def fx_highpass(self, x, sr, fc=50.0):
         x, ch = self._fx_in(x)

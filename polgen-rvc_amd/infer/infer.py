@@ -264,6 +264,20 @@ def _clean_output(hubert_model, audio_opt, tgt_sr, clean_audio, clean_strength):
     return audio_opt
 
 
+def _formant_check(formant_shift, formant_quefrency_ms):
+    """the FxFormantParams of the 16 kHz input, or None at 0.0; every refusal as ValueError before anything is read"""
+    return _lib.formant_shift_params(16000, 1, formant_shift, formant_quefrency_ms)
+
+
+def _formant_input(hubert_model, audio, params):
+    """the 16 kHz mono signal with its formants moved (include/rvcx.h stage 17), behind the cleaning, in front of VC.pipeline"""
+    if params is None:
+        return audio
+    ctx = hubert_model.ctx
+    with ctx.lock:
+        return ctx.fx_formant([np.ascontiguousarray(audio, dtype=np.float32)], 16000, params)[0].astype(np.float64)
+
+
 def rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g,
               filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
               f0_max=1100):
@@ -276,19 +290,26 @@ def rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method,
 
 def rvc_infer_clean(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g,
                     filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
-                    f0_max=1100, *, clean_audio="input", clean_strength=0.7):
+                    f0_max=1100, *, clean_audio="input", clean_strength=0.7, formant_shift=0.0, formant_quefrency_ms=1.5):
     """``rvc_infer`` with noise reduction (include/rvcx.h stage 15, adaptive mode) on the device.  clean_audio: ``None``
     (the bytes ``rvc_infer`` writes), ``"input"`` (the 16 kHz mono signal between ``load_audio`` and ``VC.pipeline``),
-    ``"output"`` (the int16 result as float32 / 32768 at ``tgt_sr``, back by clip(rint(32768 y))) or ``"both"``."""
+    ``"output"`` (the int16 result as float32 / 32768 at ``tgt_sr``, back by clip(rint(32768 y))) or ``"both"``.
+    ``formant_shift`` (semitones, -12 .. 12) is the "formant shifting" switch of the UIs: ``pitch`` moves F0 alone, this moves
+    the formants of the 16 kHz input (stage 17) behind the cleaning and in front of ``VC.pipeline``; ``formant_quefrency_ms``
+    is the resolution of its envelope.  At 0.0 nothing is launched and nothing changes."""
     _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g, filter_radius, tgt_sr,
-               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength)
+               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength,
+               formant_shift, formant_quefrency_ms)
 
 
 def _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method, cpt, version, net_g, filter_radius, tgt_sr,
-               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength):
+               volume_envelope, protect, hop_length, vc, hubert_model, f0_min, f0_max, clean_audio, clean_strength,
+               formant_shift=0.0, formant_quefrency_ms=1.5):
     from .audio import write_output
     _clean_check(clean_audio, clean_strength)
+    formant = _formant_check(formant_shift, formant_quefrency_ms)
     audio = _clean_input(hubert_model, load_audio(input_path, 16000), clean_audio, clean_strength)
+    audio = _formant_input(hubert_model, audio, formant)
     pitch_guidance = cpt.get("f0", 1)
     audio_opt = vc.pipeline(hubert_model, net_g, 0, audio, input_path, pitch, f0_method, index_path, index_rate,
                             pitch_guidance, filter_radius, tgt_sr, 0, volume_envelope, version, protect,
@@ -300,22 +321,25 @@ def _rvc_infer(index_path, index_rate, input_path, output_path, pitch, f0_method
 
 def rvc_infer_many(index_path, index_rate, input_paths, output_paths, pitch, f0_method, cpt, version, net_g,
                    filter_radius, tgt_sr, volume_envelope, protect, hop_length, vc, hubert_model, f0_min=50,
-                   f0_max=1100, *, clean_audio=None, clean_strength=0.7):
+                   f0_max=1100, *, clean_audio=None, clean_strength=0.7, formant_shift=0.0, formant_quefrency_ms=1.5):
     """``rvc_infer`` over lists of paths (the reference lists batch conversion as not done, TODO.md:11) through
     ``VC.pipeline_stream``: two conversions are in flight while the next file is decoded, and every output file holds
     the bytes ``rvc_infer`` writes for it.  A file that is not at 16 kHz is resampled on the GPU by ``load_audio``; the
     resampler is the one entry point of the context that does not complete the conversions in flight first (it works in
     a buffer of its own on the front stream, beside their synthesizer).  ``clean_audio`` / ``clean_strength``: as in
     ``rvc_infer_clean``, every file holding the bytes that function writes for it; with ``None`` nothing changes.  (The
-    cleaning is an entry point like any other: it completes the conversions in flight first.)"""
+    cleaning is an entry point like any other: it completes the conversions in flight first.)  ``formant_shift`` /
+    ``formant_quefrency_ms``: as in ``rvc_infer_clean``; at 0.0 nothing changes."""
     from .audio import write_output
     _clean_check(clean_audio, clean_strength)
+    formant = _formant_check(formant_shift, formant_quefrency_ms)
     input_paths, output_paths = list(input_paths), list(output_paths)
     if len(input_paths) != len(output_paths):
         raise ValueError("rvc_infer_many: one output path per input path")
     pitch_guidance = cpt.get("f0", 1)
     # lazy: decoded as the stream asks for them
-    clips = (_clean_input(hubert_model, load_audio(path, 16000), clean_audio, clean_strength) for path in input_paths)
+    clips = (_formant_input(hubert_model, _clean_input(hubert_model, load_audio(path, 16000), clean_audio, clean_strength), formant)
+             for path in input_paths)
     results = vc.pipeline_stream(hubert_model, net_g, 0, clips, None, pitch, f0_method, index_path, index_rate,
                                  pitch_guidance, filter_radius, tgt_sr, 0, volume_envelope, version, protect,
                                  hop_length, f0_file=None, f0_min=f0_min, f0_max=f0_max)

@@ -31,6 +31,13 @@ output_path, strength)`` cleans a file at its length, rate and channel count, ad
 (``mode="profile", noise_path=...``); ``reduce_noise_many(jobs)`` runs one device call per (rate, channel count).  The
 keyword-only ``vocal_denoise=0.0`` of ``process_audio`` and ``process_audio_many`` cleans the vocal in adaptive mode in front
 of the board; at 0.0 every file is byte for byte what it was.
+
+Formant shift (include/rvcx.h stages 17 and 18) is the "formant shifting" switch of the UIs: the spectral envelope of every
+frame is estimated on the device and replaced by a warped copy.  ``shift_formants(input_path, output_path, semitones)`` moves
+the formants of a file and leaves its pitch; ``shift_formants_many(jobs, semitones)`` runs one device call per (rate, channel
+count); ``shift_pitch(..., preserve_formants=True)`` transposes a vocal stem and keeps its formants where they were.  The
+keyword-only ``vocal_formant=0.0`` (semitones) of ``process_audio`` and ``process_audio_many`` shifts the formants of the vocal
+behind ``vocal_denoise`` and in front of the board; at 0.0 every file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -44,7 +51,8 @@ from ..infer import _state
 from ..infer.audio import convert_to_stereo, read_audio, write_output, write_wav_pcm16
 
 __all__ = ["convert_to_stereo", "add_effects", "combine_audio", "process_audio", "process_audio_many", "measure_loudness",
-           "last_master_report", "shift_pitch", "reduce_noise", "reduce_noise_many", "OUTPUT_DIR"]
+           "last_master_report", "shift_pitch", "reduce_noise", "reduce_noise_many", "shift_formants", "shift_formants_many",
+           "OUTPUT_DIR"]
 
 OUTPUT_DIR = os.path.join(os.getcwd(), "output")
 
@@ -118,19 +126,71 @@ def _shifted(ctx, x, sr, semitones):
     return _shifted_many(ctx, [x], sr, semitones)[0]
 
 
-def shift_pitch(input_path, output_path, semitones):
+def shift_pitch(input_path, output_path, semitones, *, preserve_formants=False):
     """The file transposed by `semitones` (-12 .. 12) at its own length, rate and channel count (more than two channels: the
-    first two), written as 16-bit PCM through ``write_output``.  0 copies the samples."""
+    first two), written as 16-bit PCM through ``write_output``.  0 copies the samples.  ``preserve_formants``: the spectral
+    envelope of the file is put back onto its transposed copy (include/rvcx.h stage 18) -- for a vocal stem, whose formants
+    would otherwise move with the key."""
     x, sr = read_audio(input_path)
     x = np.asarray(x)
     x = x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
-    y = _shifted(_state.context(), x, sr, semitones) if semitones else x
+    if semitones and preserve_formants:
+        if not np.isfinite(semitones) or abs(semitones) > 12.0:
+            raise ValueError(f"pitch shift of {semitones!r} semitones: a finite value within -12 .. 12 is expected")
+        ctx = _state.context()
+        with ctx.lock:
+            y = ctx.fx_pitch_shift([np.ascontiguousarray(x, dtype=np.float32)], sr, float(semitones), preserve_formants=True)[0]
+    else:
+        y = _shifted(_state.context(), x, sr, semitones) if semitones else x
     write_output(output_path, _pcm16(y), sr)
 
 
 def _two_channels(x):
     x = np.asarray(x)
     return x if x.ndim == 1 or x.shape[1] <= 2 else np.ascontiguousarray(x[:, :2])
+
+
+_formant_params = _lib.formant_shift_params     # (sr, channels, semitones, quefrency_ms, amount): every refusal as ValueError
+
+
+def _check_vocal_formant(vocal_formant):
+    """``vocal_formant`` of process_audio(_many), before the first file is written: the default quefrency fits every rate, so
+    the semitones are all there is to refuse"""
+    _formant_params(16000, 2, vocal_formant)
+
+
+def shift_formants_many(jobs, semitones, *, quefrency_ms=1.5, amount=1.0):
+    """jobs: (input_path, output_path) tuples.  The formants of every file move by `semitones` (-12 .. 12; the pitch stays)
+    through include/rvcx.h stage 17; every file keeps its length, rate and channel count (more than two channels: the first
+    two) and is written as 16-bit PCM through ``write_output``; ONE rvcx_fx_formant call per (rate, channel count).  0
+    semitones copies the samples.  Returns the output paths."""
+    jobs = [tuple(j) for j in jobs]
+    if any(len(j) != 2 for j in jobs):
+        raise ValueError("shift_formants_many: a job is (input_path, output_path)")
+    groups = {}
+    for i, j in enumerate(jobs):
+        x, sr = read_audio(j[0])
+        x = np.asarray(_two_channels(x), np.float32)
+        ch = 1 if x.ndim == 1 else x.shape[1]
+        _formant_params(sr, ch, semitones, quefrency_ms, amount)     # every refusal before the first file is written
+        groups.setdefault((sr, ch), []).append((i, x))
+    ctx = _state.context() if semitones else None
+    for (sr, ch), members in groups.items():
+        if semitones:
+            with ctx.lock:
+                ys = ctx.fx_formant([x for _, x in members], sr, _formant_params(sr, ch, semitones, quefrency_ms, amount))
+        else:
+            ys = [x for _, x in members]
+        for (i, _), y in zip(members, ys):
+            write_output(jobs[i][1], _pcm16(y), sr)
+    return [j[1] for j in jobs]
+
+
+def shift_formants(input_path, output_path, semitones, *, quefrency_ms=1.5, amount=1.0):
+    """The file with its formants moved by `semitones` (positive: brighter, a smaller vocal tract) and its pitch left alone,
+    at its own length, rate and channel count, written as 16-bit PCM through ``write_output``.  ``quefrency_ms``: the
+    resolution of the spectral envelope (lower it towards the period of a high voice); ``amount``: 0 .. 1."""
+    shift_formants_many([(input_path, output_path)], semitones, quefrency_ms=quefrency_ms, amount=amount)
 
 
 def _denoise_params(sr, channels, strength, mode, params):
@@ -296,11 +356,13 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
                   noise_gate_threshold, noise_gate_ratio, noise_gate_attack, noise_gate_release, chorus_rate_hz,
                   chorus_depth, chorus_centre_delay_ms, chorus_feedback, chorus_mix, output_format, vocal_gain,
                   instrumental_gain, use_effects, progress=None, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0,
-                  instrumental_pitch=0.0, vocal_denoise=0.0):
+                  instrumental_pitch=0.0, vocal_denoise=0.0, vocal_formant=0.0):
     """audio_processing.py:113-200 -> the path of the finished cover, OUTPUT_DIR/AiCover.<output_format>.  ``vocal_denoise``
-    (0 .. 1): the stereo vocal is cleaned in adaptive mode (``reduce_noise``) in front of the board"""
+    (0 .. 1): the stereo vocal is cleaned in adaptive mode (``reduce_noise``) in front of the board; ``vocal_formant``
+    (semitones): its formants are moved (``shift_formants``) behind that and in front of the board"""
     _check_paths(vocal_audio_path, instrumental_audio_path)
     _check_format(output_format)
+    _check_vocal_formant(vocal_formant)
     os.makedirs(OUTPUT_DIR, exist_ok=True)
     voice_stereo_path = os.path.join(OUTPUT_DIR, "Voice_Stereo.wav")
     aicover_path = os.path.join(OUTPUT_DIR, f"AiCover.{output_format}")
@@ -309,6 +371,8 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
     convert_to_stereo(vocal_audio_path, voice_stereo_path)
     if vocal_denoise:
         reduce_noise(voice_stereo_path, voice_stereo_path, vocal_denoise)
+    if vocal_formant:
+        shift_formants(voice_stereo_path, voice_stereo_path, vocal_formant)
     if use_effects:
         vocal_output_path = os.path.join(OUTPUT_DIR, "Vocal_Effected.wav")
         add_effects(voice_stereo_path, vocal_output_path, reverb_rm_size, reverb_wet, reverb_dry, reverb_damping,
@@ -324,20 +388,22 @@ def process_audio(vocal_audio_path, instrumental_audio_path, reverb_rm_size, rev
 
 
 def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_dbtp=-1.0, instrumental_pitch=0.0,
-                       vocal_denoise=0.0):
+                       vocal_denoise=0.0, vocal_formant=0.0):
     """A list of covers in one go.  Every job is the positional argument tuple of ``process_audio`` (24 values; a 25th, when
     given, is the output path -- the default is OUTPUT_DIR/AiCover_<index>.<output_format>).  The boards of all jobs that
     share a sample rate and the eighteen effect values run in ONE rvcx_fx_chain call; every cover is byte for byte what
     ``process_audio`` writes for the same arguments.  With ``target_lufs`` all covers of one rate (and one slider difference)
     are mastered in ONE rvcx_fx_master call.  ``instrumental_pitch`` transposes the instrumentals, all of one rate in ONE rvcx_fx_pitch_shift call.
-    ``vocal_denoise`` cleans the stereo vocals in front of the boards, all of one rate in ONE rvcx_fx_denoise call.  Returns the
-    list of output paths."""
+    ``vocal_denoise`` cleans the stereo vocals in front of the boards, all of one rate in ONE rvcx_fx_denoise call;
+    ``vocal_formant`` (semitones) then moves their formants, all of one rate in ONE rvcx_fx_formant call.  Returns the list of
+    output paths."""
     jobs = [tuple(j) for j in jobs]
     for j in jobs:
         if len(j) not in (24, 25):
             raise ValueError("process_audio_many: a job is the 24 positional arguments of process_audio (+ an output path)")
         _check_paths(j[0], j[1])
         _check_format(j[20])
+    _check_vocal_formant(vocal_formant)
     os.makedirs(OUTPUT_DIR, exist_ok=True)
     ctx = _state.context()
     outs = [j[24] if len(j) == 25 else os.path.join(OUTPUT_DIR, f"AiCover_{i}.{j[20]}") for i, j in enumerate(jobs)]
@@ -348,6 +414,8 @@ def process_audio_many(jobs, *, target_lufs=None, vocal_offset_lu=0.0, ceiling_d
             convert_to_stereo(j[0], vocal[i])
         if vocal_denoise:
             reduce_noise_many([(v, v) for v in vocal], vocal_denoise)
+        if vocal_formant:
+            shift_formants_many([(v, v) for v in vocal], vocal_formant)
         for i, j in enumerate(jobs):
             if j[23]:
                 x, sr = read_audio(vocal[i])
