@@ -2112,18 +2112,34 @@ class Context:
             raise RvcxError("fx: array of shape (frames,) or (frames, channels) with at least one frame expected")
         return x, (1 if x.ndim == 1 else x.shape[1])
 
+    def _fx_items(self, items, what):
+        """the input tables of a batched call: (arrays, channels, B, pointer table, frame counts)"""
+        xs = [self._fx_in(x) for x in items]
+        if not xs or any(ch != xs[0][1] for _, ch in xs):
+            raise RvcxError(f"{what}: a non-empty list of items with one channel count expected")
+        B = len(xs)
+        xp = (C.c_void_p * B)(*[x.ctypes.data for x, _ in xs])
+        n = (C.c_int64 * B)(*[x.shape[0] for x, _ in xs])
+        return [x for x, _ in xs], xs[0][1], B, xp, n
+
+    @staticmethod
+    def _fx_table(arrays):
+        """a pointer table over a list of arrays; None (or an array without a frame) gives a null entry"""
+        return (C.c_void_p * len(arrays))(*[None if a is None or a.shape[0] == 0 else a.ctypes.data for a in arrays])
+
+    def _named_timing(self, names):
+        """rvcx_last_timing's nine slots under a stage's names for them (names starting with "_" are left out)"""
+        ms = (C.c_float * 9)()
+        lib().rvcx_last_timing(self._h, ms)
+        return {k: float(v) for k, v in zip(names, ms) if not k.startswith("_")}
+
     def fx_chain(self, items, params: "FxParams"):
         """rvcx_fx_chain: the whole board on a list of (frames, 2) float32 arrays in one call -> list of arrays"""
-        xs = [self._fx_in(x)[0] for x in items]
-        for x in xs:
-            if (1 if x.ndim == 1 else x.shape[1]) != params.channels:
-                raise RvcxError("fx_chain: every item needs params.channels channels")
+        xs, ch, B, xp, n = self._fx_items(items, "fx_chain")
+        if ch != params.channels:
+            raise RvcxError("fx_chain: every item needs params.channels channels")
         ys = [np.empty_like(x) for x in xs]
-        B = len(xs)
-        xp = (C.c_void_p * max(B, 1))(*[x.ctypes.data for x in xs])
-        yp = (C.c_void_p * max(B, 1))(*[y.ctypes.data for y in ys])
-        n = (C.c_int64 * max(B, 1))(*[x.shape[0] for x in xs])
-        self._ck(lib().rvcx_fx_chain(self._h, B, xp, n, C.byref(params), yp), "fx_chain")
+        self._ck(lib().rvcx_fx_chain(self._h, B, xp, n, C.byref(params), self._fx_table(ys)), "fx_chain")
         return ys
 
     def fx_last_passes(self):
@@ -2134,43 +2150,31 @@ class Context:
 
     def fx_last_timing(self):
         """per-stage device ms of the last fx_chain call (rvcx_last_timing's nine slots under their post-production names)"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "copies", "total"]
-        return dict(zip(names, [float(v) for v in ms]))
+        return self._named_timing(["highpass", "compressor", "gate", "reverb", "low_shelf", "high_shelf", "chorus", "copies",
+                                   "total"])
 
     # ---- loudness, true peak, limiter, master (rvcx.h stages 9 - 12) --------------------------------------------------------
     def fx_loudness(self, items, sr, momentary=False):
         """rvcx_fx_loudness on a list of signals of one rate and channel count in one call -> list of (LUFS, dBTP), with
         momentary=True of (LUFS, dBTP, float32 momentary values)"""
-        xs = [self._fx_in(x) for x in items]
-        if not xs or any(ch != xs[0][1] for _, ch in xs):
-            raise RvcxError("fx_loudness: a non-empty list of items with one channel count expected")
-        B, ch = len(xs), xs[0][1]
-        xp = (C.c_void_p * B)(*[x.ctypes.data for x, _ in xs])
-        n = (C.c_int64 * B)(*[x.shape[0] for x, _ in xs])
+        xs, ch, B, xp, n = self._fx_items(items, "fx_loudness")
         L, tp = np.zeros(B, np.float64), np.zeros(B, np.float64)
-        ms = [np.zeros(max(fx_momentary_len(x.shape[0], sr), 1), np.float32) for x, _ in xs] if momentary else None
-        mp = (C.c_void_p * B)(*[m.ctypes.data for m in ms]) if momentary else None
+        ms = [np.zeros(max(fx_momentary_len(x.shape[0], sr), 1), np.float32) for x in xs] if momentary else None
+        mp = self._fx_table(ms) if momentary else None
         self._ck(lib().rvcx_fx_loudness(self._h, B, xp, n, ch, int(sr), L.ctypes.data, tp.ctypes.data, mp), "fx_loudness")
         if momentary:
-            return [(float(L[b]), float(tp[b]), ms[b][:fx_momentary_len(xs[b][0].shape[0], sr)]) for b in range(B)]
+            return [(float(L[b]), float(tp[b]), ms[b][:fx_momentary_len(xs[b].shape[0], sr)]) for b in range(B)]
         return [(float(L[b]), float(tp[b])) for b in range(B)]
 
     def fx_loudness_timing(self):
         """per-stage device ms of the last fx_loudness call"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["copies_in", "chunk_states", "carry", "kweight_energy", "gates", "true_peak", "copies_out", "unused", "total"]
-        return dict(zip(names, [float(v) for v in ms]))
+        return self._named_timing(["copies_in", "chunk_states", "carry", "kweight_energy", "gates", "true_peak", "copies_out", "unused",
+                                   "total"])
 
     def fx_master_timing(self):
         """per-stage device ms of the last fx_master call"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["stem_loudness", "mix", "mix_loudness", "scale_true_peak", "limiter_gain", "gain_int16", "result_meters",
-                 "copies", "total"]
-        return dict(zip(names, [float(v) for v in ms]))
+        return self._named_timing(["stem_loudness", "mix", "mix_loudness", "scale_true_peak", "limiter_gain", "gain_int16",
+                                   "result_meters", "copies", "total"])
 
     def fx_true_peak(self, x, want_p=False):
         """rvcx_op_fx_truepeak -> dBTP, or (dBTP, p[n])"""
@@ -2198,32 +2202,19 @@ class Context:
             raise RvcxError("fx_master: as many instrumentals as vocals, at least one, every vocal with a frame")
         B = len(vs)
         ys = [np.zeros((v.shape[0], 2), np.int16) for v in vs]
-        vp_ = (C.c_void_p * B)(*[v.ctypes.data for v in vs])
-        mp = (C.c_void_p * B)(*[m.ctypes.data if m.shape[0] else None for m in ms])
-        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
         nv = (C.c_int64 * B)(*[v.shape[0] for v in vs])
         ni = (C.c_int64 * B)(*[m.shape[0] for m in ms])
         rep = np.zeros((B, 7), np.float64)
-        self._ck(lib().rvcx_fx_master(self._h, B, vp_, nv, mp, ni, int(sr), float(target_lufs), float(vocal_offset_lu),
-                                      float(ceiling_dbtp), yp, rep.ctypes.data), "fx_master")
+        self._ck(lib().rvcx_fx_master(self._h, B, self._fx_table(vs), nv, self._fx_table(ms), ni, int(sr), float(target_lufs),
+                                      float(vocal_offset_lu), float(ceiling_dbtp), self._fx_table(ys), rep.ctypes.data), "fx_master")
         return ys, [dict(zip(MASTER_REPORT, (float(r) for r in row))) for row in rep]
 
     # ---- time stretch and pitch shift (rvcx.h stages 13 and 14) -------------------------------------------------------------
-    def _fx_items(self, items, what):
-        xs = [self._fx_in(x) for x in items]
-        if not xs or any(ch != xs[0][1] for _, ch in xs):
-            raise RvcxError(f"{what}: a non-empty list of items with one channel count expected")
-        B = len(xs)
-        xp = (C.c_void_p * B)(*[x.ctypes.data for x, _ in xs])
-        n = (C.c_int64 * B)(*[x.shape[0] for x, _ in xs])
-        return [x for x, _ in xs], xs[0][1], B, xp, n
-
     def fx_stretch(self, items, sr, P, Q):
         """rvcx_fx_stretch: a list of float32 signals of one rate and channel count, stretched by P / Q in one call"""
         xs, ch, B, xp, n = self._fx_items(items, "fx_stretch")
         ys = [np.zeros((max(fx_stretch_len(x.shape[0], P, Q), 1),) + x.shape[1:], np.float32) for x in xs]
-        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
-        self._ck(lib().rvcx_fx_stretch(self._h, B, xp, n, ch, int(sr), int(P), int(Q), yp), "fx_stretch")
+        self._ck(lib().rvcx_fx_stretch(self._h, B, xp, n, ch, int(sr), int(P), int(Q), self._fx_table(ys)), "fx_stretch")
         return [y[:fx_stretch_len(x.shape[0], P, Q)] for x, y in zip(xs, ys)]
 
     def fx_pitch_shift(self, items, sr, semitones, preserve_formants=False, formant_params=None):
@@ -2232,7 +2223,7 @@ class Context:
         FxFormantParams of that transfer (its ratio is not read)"""
         xs, ch, B, xp, n = self._fx_items(items, "fx_pitch_shift")
         ys = [np.zeros_like(x) for x in xs]
-        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
+        yp = self._fx_table(ys)
         if preserve_formants:
             p = (formant_params or FxFormantParams.make(sr, ch)).with_shape(sr, ch)
             self._ck(lib().rvcx_fx_pitch_shift_formant(self._h, B, xp, n, ch, int(sr), float(semitones), C.byref(p), yp),
@@ -2259,11 +2250,8 @@ class Context:
 
     def fx_stretch_timing(self):
         """per-kernel device ms of the last fx_stretch / fx_pitch_shift call"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["copies_in", "transforms", "owners", "scan", "inverse_transforms", "overlap_add", "resampler", "copies_out",
-                 "total"]
-        return dict(zip(names, [float(v) for v in ms]))
+        return self._named_timing(["copies_in", "transforms", "owners", "scan", "inverse_transforms", "overlap_add", "resampler",
+                                   "copies_out", "total"])
 
     # ---- noise reduction (rvcx.h stage 15) -------------------------------------------------------------------------------------
     def fx_denoise(self, items, sr, params=None, noise=None):
@@ -2278,10 +2266,8 @@ class Context:
             if len(clips) != B:
                 raise RvcxError("fx_denoise: one noise entry per item expected")
         ys = [np.zeros_like(x) for x in xs]
-        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
-        zp = (C.c_void_p * B)(*[None if z is None else z.ctypes.data for z in clips])
         zn = (C.c_int64 * B)(*[0 if z is None else z.shape[0] for z in clips])
-        self._ck(lib().rvcx_fx_denoise(self._h, B, xp, n, zp, zn, C.byref(p), yp), "fx_denoise")
+        self._ck(lib().rvcx_fx_denoise(self._h, B, xp, n, self._fx_table(clips), zn, C.byref(p), self._fx_table(ys)), "fx_denoise")
         return ys
 
     def fx_denoise_taps(self, x, sr, params=None, noise=None):
@@ -2300,10 +2286,8 @@ class Context:
 
     def fx_denoise_timing(self):
         """per-kernel device ms of the last fx_denoise call"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["copies_in", "analysis", "smoothing", "stats_or_floor", "mask", "synthesis", "overlap_add", "copies_out", "total"]
-        return dict(zip(names, [float(v) for v in ms]))
+        return self._named_timing(["copies_in", "analysis", "smoothing", "stats_or_floor", "mask", "synthesis", "overlap_add",
+                                   "copies_out", "total"])
 
     # ---- formant shift (rvcx.h stages 17 and 18; stage 18 is fx_pitch_shift(preserve_formants=True)) --------------------------
     def fx_formant(self, items, sr, params=None, source=None):
@@ -2318,9 +2302,7 @@ class Context:
                 raise RvcxError("fx_formant: one source entry per item expected")
             srcs = [_formant_source(z, x, "fx_formant") for z, x in zip(source, xs)]
         ys = [np.zeros_like(x) for x in xs]
-        yp = (C.c_void_p * B)(*[y.ctypes.data for y in ys])
-        zp = (C.c_void_p * B)(*[None if z is None else z.ctypes.data for z in srcs])
-        self._ck(lib().rvcx_fx_formant(self._h, B, xp, n, zp, C.byref(p), yp), "fx_formant")
+        self._ck(lib().rvcx_fx_formant(self._h, B, xp, n, self._fx_table(srcs), C.byref(p), self._fx_table(ys)), "fx_formant")
         return ys
 
     def fx_formant_taps(self, x, sr, params=None, source=None):
@@ -2338,10 +2320,7 @@ class Context:
 
     def fx_formant_timing(self):
         """device ms of the last fx_formant / fx_pitch_shift(preserve_formants=True) call"""
-        ms = (C.c_float * 9)()
-        lib().rvcx_last_timing(self._h, ms)
-        names = ["copies_in", "frames", "overlap_add", "copies_out", "_4", "_5", "_6", "pitch_shift", "total"]
-        return {k: float(v) for k, v in zip(names, ms) if not k.startswith("_")}
+        return self._named_timing(["copies_in", "frames", "overlap_add", "copies_out", "_4", "_5", "_6", "pitch_shift", "total"])
 
     def fx_highpass(self, x, sr, fc=50.0):
         x, ch = self._fx_in(x)

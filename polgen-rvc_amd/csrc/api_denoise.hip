@@ -1,14 +1,11 @@
 // C ABI of librvcx.so (include/rvcx.h): noise reduction (stage 15), its taps and its host twins.
-#include "api_internal.h"
+#include "api_fx_common.h"
 #include "denoise.h"
-#include "effects.h"
 
 using namespace rvcx;
 using namespace rvcx::api;
 
 namespace {
-
-long pad256(long n) { return (std::max<long>(n, 1) + 255) / 256 * 256; }
 
 struct DenoisePlan {
   int sr, Cc, nf, nt;
@@ -20,23 +17,17 @@ struct DenoisePlan {
 DenoisePlan denoise_check(const char* who_c, const rvcx_fx_denoise_params* p) {
   const std::string who(who_c);
   if (!p) fail(who + ": null parameters");
-  if (!fx_rate_ok(p->sample_rate)) fail(who + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
-  if (p->channels != 1 && p->channels != 2) fail(who + ": channels must be 1 or 2");
+  check_rate(who_c, p->sample_rate);
+  check_channels(who_c, p->channels);
   if (p->mode != 0 && p->mode != 1) fail(who + ": mode must be 0 (profile) or 1 (adaptive)");
-  const float all[8] = {p->strength, p->n_std, p->knee_db, p->thresh_mult, p->slope, p->time_constant_s, p->freq_smooth_hz,
-                        p->time_smooth_ms};
-  for (float f : all)
-    if (!std::isfinite(f)) fail(who + ": a value is not finite");
-  auto range = [&](float f, double lo, double hi, const char* name) {
-    if (!((double)f >= lo && (double)f <= hi))
-      fail(who + ": " + name + " must lie in " + std::to_string(lo) + " .. " + std::to_string(hi));
-  };
-  range(p->strength, 0.0, 1.0, "strength");
-  range(p->n_std, 0.0, 10.0, "n_std");
-  range(p->knee_db, (double)0.1f, 20.0, "knee_db");
-  range(p->thresh_mult, 0.0, 20.0, "thresh_mult");
-  range(p->slope, (double)0.1f, 100.0, "slope");
-  range(p->time_constant_s, (double)0.05f, 30.0, "time_constant_s");
+  check_finite(who_c, {p->strength, p->n_std, p->knee_db, p->thresh_mult, p->slope, p->time_constant_s, p->freq_smooth_hz,
+                       p->time_smooth_ms});
+  check_range(who_c, p->strength, 0.0, 1.0, "strength");
+  check_range(who_c, p->n_std, 0.0, 10.0, "n_std");
+  check_range(who_c, p->knee_db, (double)0.1f, 20.0, "knee_db");
+  check_range(who_c, p->thresh_mult, 0.0, 20.0, "thresh_mult");
+  check_range(who_c, p->slope, (double)0.1f, 100.0, "slope");
+  check_range(who_c, p->time_constant_s, (double)0.05f, 30.0, "time_constant_s");
   if (p->freq_smooth_hz < 0.f || p->time_smooth_ms < 0.f) fail(who + ": freq_smooth_hz and time_smooth_ms must not be negative");
   DenoisePlan P;
   P.sr = p->sample_rate, P.Cc = p->channels, P.g = fx_stretch_geom(p->sample_rate);
@@ -47,10 +38,6 @@ DenoisePlan denoise_check(const char* who_c, const rvcx_fx_denoise_params* p) {
   P.v = FxDenoiseValues{p->mode, p->strength, p->n_std, p->knee_db, p->thresh_mult, p->slope, p->time_constant_s,
                         p->freq_smooth_hz, p->time_smooth_ms};
   return P;
-}
-
-void length_check(const std::string& who, int64_t n) {
-  if (n < 1 || n > (int64_t)1 << 30) fail(who + ": every item needs 1 .. 2^30 frames");
 }
 
 void noise_check(const std::string& who, const DenoisePlan& P, const float* noise, int64_t n_noise) {
@@ -89,61 +76,47 @@ void run_denoise(rvcx_ctx* ctx, Ctx* C, const DenoisePlan& P, int B, const float
     return (size_t)Cc * (per_row + 16 * 256 + 64);
   };
   const size_t table_bytes = (size_t)g.N * 8 + ((size_t)1 << 20);
-  const size_t budget = arena_budget(*C);
   long n_max = 0, c_max = 0;
   for (int b = 0; b < B; ++b) {
     n_max = std::max<long>(n_max, (long)n[b]), c_max = std::max(c_max, clip_len(b));
-    const size_t own = item_bytes((long)n[b], clip_len(b)) + table_bytes;
-    if (own > budget)
-      fail("fx_denoise: item " + std::to_string(b) + " of " + std::to_string((long)n[b]) + " frames needs " + std::to_string(own) +
-           " bytes, the arena budget is " + std::to_string(budget) + " (one item is not cut into segments)");
+    check_item_fits("fx_denoise", *C, b, n[b], item_bytes((long)n[b], clip_len(b)) + table_bytes);
   }
-  const char* cap = getenv("RVCX_MAX_BATCH");
-  const size_t most = cap ? (size_t)std::max(1, atoi(cap)) : (size_t)B;
-  const int G = (int)std::max<size_t>(
-      1, std::min<size_t>(std::min<size_t>(most, (size_t)B), (budget - table_bytes) / item_bytes(n_max, c_max)));
+  const size_t worst = item_bytes(n_max, c_max);
+  const int G = fx_group_size(*C, B, worst, table_bytes);
   Arena& A = C->arena;
   A.reset();
-  A.reserve(item_bytes(n_max, c_max) * std::min(G, B) + table_bytes);
+  A.reserve(worst * G + table_bytes);
   hipStream_t s = C->stream;
-  C->timer.make();
-  hipEvent_t* ev = C->timer.ev;
-  float ms[9] = {0};
-  std::vector<float> w;
-  std::vector<float2> tw;
-  fx_stretch_tables(g.N, w, tw);
+  FxTimer T(*C);
+  const StftTables tables(g.N);
   int groups = 0;
   for (int g0 = 0; g0 < B; g0 += G, ++groups) {
     const int Bg = std::min(G, B - g0), R = Bg * Cc;
     // the group's distinct clips: a clip that several items share is analysed once
-    std::vector<std::pair<const float*, long>> clips;
+    std::vector<std::pair<const float*, int64_t>> clips;
     std::vector<int> clip_of((size_t)Bg, -1);
     long nmax = 0, cmax = 0;
     for (int b = 0; b < Bg; ++b) {
       nmax = std::max<long>(nmax, (long)n[g0 + b]);
       if (clip_len(g0 + b) < 1) continue;
-      const std::pair<const float*, long> key(noise[g0 + b], clip_len(g0 + b));
+      const std::pair<const float*, int64_t> key(noise[g0 + b], clip_len(g0 + b));
       size_t u = 0;
       while (u < clips.size() && clips[u] != key) ++u;
       if (u == clips.size()) clips.push_back(key);
       clip_of[b] = (int)u;
-      cmax = std::max(cmax, key.second);
+      cmax = std::max<long>(cmax, key.second);
     }
     const int U = (int)clips.size(), Rn = U * Cc;
     const long ld = pad256(nmax), ldn = pad256(cmax);
     A.reset();
-    float* dw = A.alloc<float>((size_t)g.N);
-    float2* dtw = A.alloc<float2>((size_t)g.N / 2);
-    RVCX_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
-    RVCX_HIP(hipMemcpyAsync(dtw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice, s));
     FxDenoiseDev d{};
-    d.g = g, d.v = P.v, d.nf = P.nf, d.nt = P.nt, d.w = dw, d.tw = dtw;
+    tables.upload(*C, d.w, d.tw);
+    d.g = g, d.v = P.v, d.nf = P.nf, d.nt = P.nt;
     d.c = fx_denoise_c(g.H, P.sr, P.v.time_constant_s);
     float* stage = A.alloc<float>((size_t)R * ld);
     float* rows = A.alloc<float>((size_t)R * ld);
     float* ys = A.alloc<float>((size_t)R * ld);
-    int* dlen = A.alloc<int>((size_t)R + (size_t)std::max(Rn, 1) + (size_t)R);
-    d.it.R = R, d.it.ld = ld, d.it.Tf = fx_stretch_T(nmax, g.H), d.it.len = dlen, d.it.x = rows;
+    d.it.R = R, d.it.ld = ld, d.it.Tf = fx_stretch_T(nmax, g.H), d.it.x = rows;
     const size_t fb = (size_t)R * d.it.Tf * nb;
     d.it.D = A.alloc<float2>(fb);
     d.it.A2 = A.alloc<float>(fb);
@@ -159,65 +132,41 @@ void run_denoise(rvcx_ctx* ctx, Ctx* C, const DenoisePlan& P, int B, const float
     if (U > 0) {
       stage_n = A.alloc<float>((size_t)Rn * ldn);
       rows_n = A.alloc<float>((size_t)Rn * ldn);
-      d.nz.R = Rn, d.nz.ld = ldn, d.nz.Tf = fx_stretch_T(cmax, g.H), d.nz.len = dlen + R, d.nz.x = rows_n;
+      d.nz.R = Rn, d.nz.ld = ldn, d.nz.Tf = fx_stretch_T(cmax, g.H), d.nz.x = rows_n;
       d.nz.A2 = A.alloc<float>((size_t)Rn * d.nz.Tf * nb);
       d.nz.S = A.alloc<float>((size_t)Rn * d.nz.Tf * nb);
     }
-    d.prof = dlen + R + std::max(Rn, 1);
-    std::vector<int> len((size_t)R + (size_t)std::max(Rn, 1) + (size_t)R, 0);
-    for (int r = 0; r < R; ++r) {
-      len[r] = (int)n[g0 + r / Cc];
-      len[(size_t)R + std::max(Rn, 1) + r] = clip_of[r / Cc] < 0 ? -1 : clip_of[r / Cc] * Cc + r % Cc;
-    }
+    // the items' rows, the clips' rows (one entry at the least), and per item row the clip row of its profile (-1: none)
+    std::vector<int> len = row_lengths(n + g0, Bg, Cc);
+    len.resize((size_t)R + (size_t)std::max(Rn, 1) + (size_t)R, 0);
     for (int r = 0; r < Rn; ++r) len[(size_t)R + r] = (int)clips[r / Cc].second;
-    RVCX_HIP(hipEventRecord(ev[0], s));
-    RVCX_HIP(hipMemcpyAsync(dlen, len.data(), len.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * Cc, x[g0 + b], (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    launch_fx_deinterleave(stage, rows, dlen, Bg, Cc, ld, s);
-    if (U > 0) {
-      for (int u = 0; u < U; ++u)
-        RVCX_HIP(hipMemcpyAsync(stage_n + (size_t)u * ldn * Cc, clips[u].first, (size_t)clips[u].second * Cc * 4, hipMemcpyDefault, s));
-      launch_fx_deinterleave(stage_n, rows_n, d.nz.len, U, Cc, ldn, s);
-    }
-    RVCX_HIP(hipEventRecord(ev[1], s));
-    launch_denoise_analysis(d, s, ev + 2);
+    for (int r = 0; r < R; ++r) len[(size_t)R + std::max(Rn, 1) + r] = clip_of[r / Cc] < 0 ? -1 : clip_of[r / Cc] * Cc + r % Cc;
+    T.mark(0);
+    const int* dlen = to_dev(*C, len.data(), len.size());
+    d.it.len = dlen, d.nz.len = U > 0 ? dlen + R : nullptr, d.prof = dlen + R + std::max(Rn, 1);
+    stage_in([&](int b) { return std::make_pair(x[g0 + b], n[g0 + b]); }, Bg, Cc, ld, stage, rows, dlen, s);
+    if (U > 0) stage_in([&](int u) { return clips[u]; }, U, Cc, ldn, stage_n, rows_n, d.nz.len, s);
+    T.mark(1);
+    launch_denoise_analysis(d, s, T.ev + 2);
     const size_t cnt = (size_t)fx_stretch_T(len[0], g.H) * nb;               // taps: one row
     // (stream order: D leaves before the synthesis writes the frames over it, m after the mask took A2's place)
     if (taps.D) RVCX_HIP(hipMemcpyAsync(taps.D, d.it.D, cnt * 8, hipMemcpyDefault, s));
     if (taps.S) RVCX_HIP(hipMemcpyAsync(taps.S, d.it.S, cnt * 4, hipMemcpyDefault, s));
-    launch_denoise_mask(d, s, ev + 4);
+    launch_denoise_mask(d, s, T.ev + 4);
     if (taps.mu) RVCX_HIP(hipMemcpyAsync(taps.mu, d.mu, nb * 8, hipMemcpyDefault, s));
     if (taps.sd) RVCX_HIP(hipMemcpyAsync(taps.sd, d.sd, nb * 8, hipMemcpyDefault, s));
     if (taps.b) RVCX_HIP(hipMemcpyAsync(taps.b, d.b, cnt * 8, hipMemcpyDefault, s));
     if (taps.m) RVCX_HIP(hipMemcpyAsync(taps.m, d.it.A2, cnt * 4, hipMemcpyDefault, s));
-    launch_denoise_synthesis(d, ys, ld, s, ev + 6);
-    launch_fx_interleave(ys, stage, dlen, Bg, Cc, ld, s);
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(y[g0 + b], stage + (size_t)b * ld * Cc, (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    RVCX_HIP(hipEventRecord(ev[8], s));
+    launch_denoise_synthesis(d, ys, ld, s, T.ev + 6);
+    stage_out(ys, dlen, Bg, Cc, ld, stage, s, [&](int b) { return std::make_pair(y[g0 + b], n[g0 + b]); });
+    T.mark(8);
     RVCX_HIP(hipStreamSynchronize(s));
-    for (int k = 0; k < 8; ++k) {
-      float t = 0.f;
-      RVCX_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-      ms[k] += t, ms[8] += t;
-    }
+    // {copies in + layout, analysis, smoothing, statistics or floor, mask, synthesis, overlap-add, copies back, total}
+    for (int k = 0; k < 8; ++k) T.ms[8] += T.add(k, k, k + 1);
   }
   A.reset();
-  // {copies in + layout, analysis, smoothing, statistics or floor, mask, synthesis, overlap-add, copies back, total}
-  std::copy(ms, ms + 9, C->timing);
+  T.store(*C);
   ctx->fx_groups = groups;
-}
-
-template <typename F>
-int host_call(F&& body) {
-  try {
-    body();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
 }
 
 }  // namespace
@@ -233,8 +182,8 @@ int rvcx_fx_denoise_tiles(int32_t* tile_t, int32_t* tile_k, int32_t* stat_chunk)
 
 int rvcx_fx_denoise_frames(int64_t n, int sr, int64_t* T, int32_t* N, int32_t* nf, int32_t* nt) {
   return host_call([&] {
-    if (!fx_rate_ok(sr)) fail("fx_denoise_frames: the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
-    length_check("fx_denoise_frames", n);
+    check_rate("fx_denoise_frames", sr);
+    check_frames("fx_denoise_frames", n);
     const FxStretchGeom g = fx_stretch_geom(sr);
     if (T) *T = fx_stretch_T((long)n, g.H);
     if (N) *N = g.N;
@@ -249,18 +198,12 @@ int rvcx_fx_denoise(rvcx_ctx* ctx, int B, const float* const* x, const int64_t* 
   const DenoisePlan P = denoise_check("fx_denoise", params);
   if (B < 1 || !x || !n || !y) fail("fx_denoise: null argument or B < 1");
   if (noise && !n_noise) fail("fx_denoise: noise clips without their lengths");
-  for (int b = 0; b < B; ++b) {
+  for (int b = 0; b < B; ++b) {      // (not check_items: an item's clip is refused before the next item's pointers)
     if (!x[b] || !y[b]) fail("fx_denoise: null pointer in a table");
-    length_check("fx_denoise", n[b]);
+    check_frames("fx_denoise", n[b]);
     if (noise) noise_check("fx_denoise", P, noise[b], n_noise[b]);
   }
-  if (P.v.strength == 0.f) {          // skip: nothing is launched, the output is the input bit for bit
-    for (int b = 0; b < B; ++b)
-      if (y[b] != x[b]) RVCX_HIP(hipMemcpy(y[b], x[b], (size_t)n[b] * P.Cc * 4, hipMemcpyDefault));
-    std::fill(C->timing, C->timing + 9, 0.f);
-    ctx->fx_groups = 0;
-    return;
-  }
+  if (P.v.strength == 0.f) return fx_skip(ctx, B, x, n, P.Cc, y);
   run_denoise(ctx, C, P, B, x, n, noise, n_noise, y, DenoiseTaps{});
   API_END
 }
@@ -271,7 +214,7 @@ int rvcx_op_fx_denoise_taps(rvcx_ctx* ctx, const float* x, int64_t n, const floa
   API_BEGIN(ctx)
   const DenoisePlan P = denoise_check("op_fx_denoise_taps", params);
   if (!x || !y) fail("op_fx_denoise_taps: null pointer");
-  length_check("op_fx_denoise_taps", n);
+  check_frames("op_fx_denoise_taps", n);
   noise_check("op_fx_denoise_taps", P, noise, n_noise);
   DenoiseTaps t;
   t.D = D, t.S = S, t.mu = mu, t.sd = sd, t.b = b, t.m = m;
@@ -287,7 +230,7 @@ int rvcx_fx_denoise_host(const float* x, int64_t n, const float* noise, int64_t 
   return host_call([&] {
     const DenoisePlan P = denoise_check("fx_denoise_host", params);
     if (!x || !y) fail("fx_denoise_host: null pointer");
-    length_check("fx_denoise_host", n);
+    check_frames("fx_denoise_host", n);
     noise_check("fx_denoise_host", P, noise, n_noise);
     DenoiseTaps t;
     t.D = D, t.S = S, t.mu = mu, t.sd = sd, t.b = b, t.m = m;
@@ -297,14 +240,12 @@ int rvcx_fx_denoise_host(const float* x, int64_t n, const float* noise, int64_t 
       if (y != x) std::memcpy(y, x, (size_t)n * P.Cc * 4);
       return;
     }
-    std::vector<float> plane((size_t)n), clip((size_t)(noise ? n_noise : 0)), out((size_t)n);
-    for (int c = 0; c < P.Cc; ++c) {
-      for (int64_t i = 0; i < n; ++i) plane[i] = x[i * P.Cc + c];
-      if (noise)
-        for (int64_t i = 0; i < n_noise; ++i) clip[i] = noise[i * P.Cc + c];
-      fx_denoise_host(plane.data(), (long)n, noise ? clip.data() : nullptr, (long)n_noise, P.sr, P.v, out.data(), D, S, mu, sd, b, m);
-      for (int64_t i = 0; i < n; ++i) y[i * P.Cc + c] = out[i];
-    }
+    std::vector<float> clip, out((size_t)n);
+    host_planes(x, n, P.Cc, y, n, [&](int c, const float* plane) {
+      if (noise) take_plane(noise, n_noise, P.Cc, c, clip);
+      fx_denoise_host(plane, (long)n, noise ? clip.data() : nullptr, (long)n_noise, P.sr, P.v, out.data(), D, S, mu, sd, b, m);
+      return out.data();
+    });
   });
 }
 

@@ -1,6 +1,5 @@
 // C ABI of librvcx.so (include/rvcx.h): post-production -- the effects chain, its stages one by one, the mix, the host twins.
-#include "api_internal.h"
-#include "effects.h"
+#include "api_fx_common.h"
 
 using namespace rvcx;
 using namespace rvcx::api;
@@ -8,19 +7,14 @@ using namespace rvcx::api;
 namespace rvcx {
 namespace api {
 
-static void fx_check_common(const char* who, int sr, int channels, bool low_rate) {
-  if (!fx_live_rate_ok(sr, low_rate))
-    fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000" +
-         (low_rate ? " (or 3200 .. 7900 for a reduced-size voice model)" : ""));
-  if (channels != 1 && channels != 2) fail(std::string(who) + ": channels must be 1 or 2");
-}
-
 // every refusal of a plan, before anything is written
 void fx_validate(const char* who, const FxPlan& P) {
-  fx_check_common(who, P.sr, P.C, P.low_rate);
-  auto finite = [&](double v, const char* what) {
-    if (!std::isfinite(v)) fail(std::string(who) + ": " + what + " is not finite");
-  };
+  if (!P.low_rate) check_rate(who, P.sr);
+  else if (!fx_live_rate_ok(P.sr, true))         // a live session's board: the same text with its rider
+    fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000" +
+         " (or 3200 .. 7900 for a reduced-size voice model)");
+  check_channels(who, P.C);
+  auto finite = [&](double v, const char* what) { check_finite(who, {v}, what); };   // the chain names the value
   if (P.hp) {
     finite(P.hp_fc, "fc");
     if (!(P.hp_fc > 0.0 && P.hp_fc < 0.5 * P.sr)) fail(std::string(who) + ": fc must lie inside (0, sr / 2)");
@@ -78,37 +72,23 @@ size_t fx_item_bytes(const FxPlan& P, long ld) {
   return (size_t)ld * 4 * ((size_t)P.C * 5 + (P.reverb ? 16 : 0)) + (size_t)P.C * nch * 4 * 7 + 4096;
 }
 
-long fx_ld(int64_t n) { return (long)((n + kFxChunk - 1) / kFxChunk) * kFxChunk; }
-
 // B items through the stages of P.  env (optional): per item the envelope of the LAST dynamics stage of the plan.
 void fx_run(rvcx_ctx* h, Ctx* C, const char* who, int B, const float* const* x, const int64_t* n, const FxPlan& P,
             float* const* y, float* const* env) {
-  if (B < 1 || !x || !n || !y) fail(std::string(who) + ": null argument or B < 1");
-  int64_t n_max = 0;
-  for (int b = 0; b < B; ++b) {
-    if (!x[b] || !y[b] || (env && !env[b])) fail(std::string(who) + ": null pointer in a table");
-    if (n[b] < 1 || n[b] > (int64_t)1 << 30) fail(std::string(who) + ": every item needs 1 .. 2^30 frames");
-    n_max = std::max(n_max, n[b]);
-  }
+  check_items(who, B, x, n, y);
   fx_validate(who, P);
-  // groups: as many items as the activation budget holds at the longest item's size (and RVCX_MAX_BATCH allows)
-  const char* cap = getenv("RVCX_MAX_BATCH");
-  const size_t most = cap ? (size_t)std::max(1, atoi(cap)) : (size_t)B;
-  const int G = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(most, (size_t)B),
-                                                          arena_budget(*C) / fx_item_bytes(P, fx_ld(n_max))));
+  const size_t worst = fx_item_bytes(P, fx_ld(*std::max_element(n, n + B)));
+  const int G = fx_group_size(*C, B, worst, 0);
   Arena& A = C->arena;
   A.reset();
-  A.reserve(fx_item_bytes(P, fx_ld(n_max)) * G + ((size_t)1 << 20));
+  A.reserve(worst * G + ((size_t)1 << 20));
   hipStream_t s = C->stream;
-  C->timer.make();
-  hipEvent_t* ev = C->timer.ev;
-  float ms[9] = {0};
+  FxTimer T(*C);
   int passes[3] = {0, 0, 0}, groups = 0;
   const int Cc = P.C;
   for (int g0 = 0; g0 < B; g0 += G, ++groups) {
     const int Bg = std::min(G, B - g0), R = Bg * Cc;
-    long ld = 0;
-    for (int b = 0; b < Bg; ++b) ld = std::max(ld, fx_ld(n[g0 + b]));
+    const long ld = fx_ld(*std::max_element(n + g0, n + g0 + Bg));
     const size_t nch = (size_t)(ld / kFxChunk), plane = (size_t)R * ld;
     A.reset();
     float* stage = A.alloc<float>(plane);
@@ -117,23 +97,19 @@ void fx_run(rvcx_ctx* h, Ctx* C, const char* who, int B, const float* const* x, 
     float* combs = P.reverb ? A.alloc<float>((size_t)Bg * 16 * ld) : nullptr;
     float* scan = A.alloc<float>(4 * (size_t)R * nch);
     float* fstate = A.alloc<float>(3 * (size_t)R * nch + 64);
-    int* dlen = A.alloc<int>((size_t)R);
-    std::vector<int> len((size_t)R);
-    for (int r = 0; r < R; ++r) len[r] = (int)n[g0 + r / Cc];
-    RVCX_HIP(hipEventRecord(ev[0], s));
-    RVCX_HIP(hipMemcpyAsync(dlen, len.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, s));
+    const std::vector<int> len = row_lengths(n + g0, Bg, Cc);
+    T.mark(0);
+    const int* dlen = to_dev(*C, len.data(), len.size());
     RVCX_HIP(hipMemsetAsync(buf[0], 0, 4 * plane * sizeof(float), s));       // the four planes are one after the other
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * Cc, x[g0 + b], (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
     float *cur = buf[0], *nxt = buf[1], *e1 = buf[2], *e2 = buf[3];
     const float* env_dev = nullptr;
-    launch_fx_deinterleave(stage, cur, dlen, Bg, Cc, ld, s);
-    RVCX_HIP(hipEventRecord(ev[1], s));
+    stage_in([&](int b) { return std::make_pair(x[g0 + b], n[g0 + b]); }, Bg, Cc, ld, stage, cur, dlen, s);
+    T.mark(1);
     if (P.hp) {
       launch_fx_biquad(fx_coeffs(0, P.sr, P.hp_fc, 0.0, 0.0), cur, nxt, dlen, R, ld, scan, s);
       std::swap(cur, nxt);
     }
-    RVCX_HIP(hipEventRecord(ev[2], s));
+    T.mark(2);
     if (P.comp) {
       const int p = launch_fx_follower(cur, e2, dlen, len.data(), R, ld, 0, 0, fx_cte(P.comp_att, P.sr), fx_cte(P.comp_rel, P.sr),
                                        fstate, s);
@@ -142,7 +118,7 @@ void fx_run(rvcx_ctx* h, Ctx* C, const char* who, int B, const float* const* x, 
       std::swap(cur, nxt);
       env_dev = e2;
     }
-    RVCX_HIP(hipEventRecord(ev[3], s));
+    T.mark(3);
     if (P.gate) {
       int p = launch_fx_follower(cur, e1, dlen, len.data(), R, ld, 1, 1, fx_cte(0.0, P.sr), fx_cte(50.0, P.sr), fstate, s);
       passes[1] = std::max(passes[1], p);
@@ -152,65 +128,38 @@ void fx_run(rvcx_ctx* h, Ctx* C, const char* who, int B, const float* const* x, 
       std::swap(cur, nxt);
       env_dev = e2;
     }
-    RVCX_HIP(hipEventRecord(ev[4], s));
+    T.mark(4);
     if (P.reverb) {
       launch_fx_reverb(fx_reverb_setup(P.sr, P.room, P.damp, P.wet, P.dry, P.width), cur, combs, e1, nxt, dlen, Bg, ld, s);
       std::swap(cur, nxt);
     }
-    RVCX_HIP(hipEventRecord(ev[5], s));
+    T.mark(5);
     if (P.lo) {
       launch_fx_biquad(fx_coeffs(1, P.sr, P.lo_fc, P.lo_q, P.lo_db), cur, nxt, dlen, R, ld, scan, s);
       std::swap(cur, nxt);
     }
-    RVCX_HIP(hipEventRecord(ev[6], s));
+    T.mark(6);
     if (P.hi) {
       launch_fx_biquad(fx_coeffs(2, P.sr, P.hi_fc, P.hi_q, P.hi_db), cur, nxt, dlen, R, ld, scan, s);
       std::swap(cur, nxt);
     }
-    RVCX_HIP(hipEventRecord(ev[7], s));
+    T.mark(7);
     if (P.chorus) {
       launch_fx_chorus(fx_chorus_setup(P.sr, P.rate, P.depth, P.centre, P.fb, P.mix), cur, e1, nxt, dlen, R, ld, s);
       std::swap(cur, nxt);
     }
-    RVCX_HIP(hipEventRecord(ev[8], s));
-    launch_fx_interleave(cur, stage, dlen, Bg, Cc, ld, s);
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(y[g0 + b], stage + (size_t)b * ld * Cc, (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    if (env && env_dev) {
-      launch_fx_interleave(env_dev, stage, dlen, Bg, Cc, ld, s);
-      for (int b = 0; b < Bg; ++b)
-        RVCX_HIP(hipMemcpyAsync(env[g0 + b], stage + (size_t)b * ld * Cc, (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    }
-    RVCX_HIP(hipEventRecord(ev[9], s));
+    T.mark(8);
+    stage_out(cur, dlen, Bg, Cc, ld, stage, s, [&](int b) { return std::make_pair(y[g0 + b], n[g0 + b]); });
+    if (env && env_dev) stage_out(env_dev, dlen, Bg, Cc, ld, stage, s, [&](int b) { return std::make_pair(env[g0 + b], n[g0 + b]); });
+    T.mark(9);
     RVCX_HIP(hipStreamSynchronize(s));
-    float t = 0.f;
-    for (int k = 0; k < 7; ++k) {
-      RVCX_HIP(hipEventElapsedTime(&t, ev[k + 1], ev[k + 2]));
-      ms[k] += t;
-    }
-    RVCX_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
-    ms[7] += t;
-    RVCX_HIP(hipEventElapsedTime(&t, ev[8], ev[9]));
-    ms[7] += t;
-    RVCX_HIP(hipEventElapsedTime(&t, ev[0], ev[9]));
-    ms[8] += t;
+    // {the seven stages, copies + layout at either end, total}
+    T.add_each(0, 1, 7), T.add(7, 0, 1), T.add(7, 8, 9), T.add(8, 0, 9);
   }
   A.reset();
-  std::copy(ms, ms + 9, C->timing);
+  T.store(*C);
   std::copy(passes, passes + 3, h->fx_passes);
   h->fx_groups = groups;
-}
-
-// the host twins have no context: the message goes where rvcx_last_error(NULL) reads it
-template <typename F>
-int fx_host_call(F&& body) {
-  try {
-    body();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
 }
 
 void fx_host_args(const char* who, const void* x, int64_t n, const void* y) {
@@ -301,7 +250,7 @@ int rvcx_op_fx_mix(rvcx_ctx* ctx, const int16_t* vocal, int64_t n_v, const int16
   API_BEGIN(ctx)
   if (n_v < 0 || n_i < 0 || n_v > (int64_t)1 << 30 || n_i > (int64_t)1 << 30) fail("op_fx_mix: frame counts must lie in 0 .. 2^30");
   if ((n_v && (!vocal || !out)) || (n_i && !inst)) fail("op_fx_mix: null argument");
-  if (!std::isfinite(vocal_gain_db) || !std::isfinite(inst_gain_db)) fail("op_fx_mix: a gain is not finite");
+  check_finite("op_fx_mix", {vocal_gain_db, inst_gain_db}, "a gain");
   if (n_v == 0) return;
   const size_t nv = (size_t)n_v * 2, ni = (size_t)std::min(n_i, n_v) * 2;
   C->arena.reset();
@@ -333,10 +282,10 @@ float rvcx_fx_cte(double ms, int sr) { return fx_cte(ms, sr); }
 int rvcx_fx_delay(int sr, int D) { return fx_delay(sr, D); }
 
 int rvcx_fx_coeffs(int kind, int sr, double fc, double Q, double gain_db, float* coef5) {
-  return fx_host_call([&] {
+  return host_call([&] {
     if (!coef5) fail("fx_coeffs: null pointer");
     if (kind < 0 || kind > 2) fail("fx_coeffs: kind must be 0, 1 or 2");
-    if (!fx_rate_ok(sr)) fail("fx_coeffs: the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
+    check_rate("fx_coeffs", sr);
     if (!(fc > 0.0 && fc < 0.5 * sr) || (kind && !(Q > 0.0)) || !std::isfinite(gain_db)) fail("fx_coeffs: fc inside (0, sr / 2), Q > 0, finite gain");
     const FxBiquad q = fx_coeffs(kind, sr, fc, Q, gain_db);
     coef5[0] = q.b0, coef5[1] = q.b1, coef5[2] = q.b2, coef5[3] = q.a1, coef5[4] = q.a2;
@@ -344,16 +293,16 @@ int rvcx_fx_coeffs(int kind, int sr, double fc, double Q, double gain_db, float*
 }
 
 int rvcx_fx_highpass_host(const float* x, int64_t n, int sr, float fc, float* y) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_highpass_host", x, n, y);
-    if (!fx_rate_ok(sr)) fail("fx_highpass_host: the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
+    check_rate("fx_highpass_host", sr);
     if (!(fc > 0.f && fc < 0.5f * sr)) fail("fx_highpass_host: fc must lie inside (0, sr / 2)");
     fx_highpass_host(fx_coeffs(0, sr, fc, 0.0, 0.0), x, (long)n, y);
   });
 }
 
 int rvcx_fx_biquad_host(const float* x, int64_t n, const float* c, float* y) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_biquad_host", x, n, y);
     if (!c) fail("fx_biquad_host: null coefficients");
     fx_biquad_host(FxBiquad{c[0], c[1], c[2], c[3], c[4]}, x, (long)n, y);
@@ -361,7 +310,7 @@ int rvcx_fx_biquad_host(const float* x, int64_t n, const float* c, float* y) {
 }
 
 int rvcx_fx_follower_host(const float* x, int64_t n, int square, int sqrt_out, float c_attack, float c_release, float* env) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_follower_host", x, n, env);
     if (!(c_attack >= 0.f && c_attack < 1.f && c_release >= 0.f && c_release < 1.f)) fail("fx_follower_host: constants must lie in [0, 1)");
     fx_follower_host(x, (long)n, square, sqrt_out, c_attack, c_release, env);
@@ -395,16 +344,16 @@ static void fx_dynamics_host(const char* who, int gate, const float* x, int64_t 
 
 int rvcx_fx_compressor_host(const float* x, int64_t n, int sr, float ratio, float threshold_db, float attack_ms,
                             float release_ms, float* y, float* env) {
-  return fx_host_call([&] { fx_dynamics_host("fx_compressor_host", 0, x, n, sr, ratio, threshold_db, attack_ms, release_ms, y, env); });
+  return host_call([&] { fx_dynamics_host("fx_compressor_host", 0, x, n, sr, ratio, threshold_db, attack_ms, release_ms, y, env); });
 }
 
 int rvcx_fx_gate_host(const float* x, int64_t n, int sr, float threshold_db, float ratio, float attack_ms, float release_ms,
                       float* y, float* env) {
-  return fx_host_call([&] { fx_dynamics_host("fx_gate_host", 1, x, n, sr, ratio, threshold_db, attack_ms, release_ms, y, env); });
+  return host_call([&] { fx_dynamics_host("fx_gate_host", 1, x, n, sr, ratio, threshold_db, attack_ms, release_ms, y, env); });
 }
 
 int rvcx_fx_comb_host(const float* in, int64_t n, int D, float fb, float d, float* out) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_comb_host", in, n, out);
     if (D < 1 || !(std::fabs(fb) < 1.f) || !(d >= 0.f && d < 1.f)) fail("fx_comb_host: D >= 1, |fb| < 1 and d in [0, 1)");
     fx_comb_host(in, (long)n, D, fb, d, out);
@@ -412,7 +361,7 @@ int rvcx_fx_comb_host(const float* in, int64_t n, int D, float fb, float d, floa
 }
 
 int rvcx_fx_allpass_host(const float* in, int64_t n, int D, float* out) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_allpass_host", in, n, out);
     if (D < 1) fail("fx_allpass_host: D >= 1");
     fx_allpass_host(in, (long)n, D, out);
@@ -421,7 +370,7 @@ int rvcx_fx_allpass_host(const float* in, int64_t n, int D, float* out) {
 
 int rvcx_fx_chorus_host(const float* x, int64_t n, int sr, float rate_hz, float depth, float centre_delay_ms, float feedback,
                         float mix, float* y) {
-  return fx_host_call([&] {
+  return host_call([&] {
     fx_host_args("fx_chorus_host", x, n, y);
     FxPlan P;
     P.sr = sr, P.C = 1, P.chorus = true, P.rate = rate_hz, P.depth = depth, P.centre = centre_delay_ms, P.fb = feedback, P.mix = mix;
@@ -437,10 +386,10 @@ int rvcx_fx_chorus_host(const float* x, int64_t n, int sr, float rate_hz, float 
 
 int rvcx_fx_mix_host(const int16_t* vocal, int64_t n_v, const int16_t* inst, int64_t n_i, float vocal_gain_db,
                      float inst_gain_db, int16_t* out) {
-  return fx_host_call([&] {
+  return host_call([&] {
     if (n_v < 0 || n_i < 0) fail("fx_mix_host: negative frame count");
     if ((n_v && (!vocal || !out)) || (n_i && !inst)) fail("fx_mix_host: null pointer");
-    if (!std::isfinite(vocal_gain_db) || !std::isfinite(inst_gain_db)) fail("fx_mix_host: a gain is not finite");
+    check_finite("fx_mix_host", {vocal_gain_db, inst_gain_db}, "a gain");
     fx_mix_host(vocal, (long)n_v * 2, inst, (long)std::min(n_i, n_v) * 2, std::pow(10.0, (double)vocal_gain_db / 20.0),
                 std::pow(10.0, (double)inst_gain_db / 20.0), out);
   });

@@ -1,7 +1,6 @@
 // C ABI of librvcx.so (include/rvcx.h): loudness metering, true peak, limiter and the loudness-matched master (stages 9 - 12),
 // and their host twins.
-#include "api_internal.h"
-#include "effects.h"
+#include "api_fx_common.h"
 #include "effects_device.h"
 
 // the host twins' roundings are written out, as in loudness.hip
@@ -12,16 +11,13 @@ using namespace rvcx::api;
 
 namespace {
 
-long fx_ld(int64_t n) { return (long)((std::max<int64_t>(n, 1) + kFxChunk - 1) / kFxChunk) * kFxChunk; }
-
 void loud_check(const char* who, int sr, int channels) {
-  if (!fx_rate_ok(sr)) fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
-  if (channels != 1 && channels != 2) fail(std::string(who) + ": channels must be 1 or 2");
+  check_rate(who, sr);
+  check_channels(who, channels);
 }
 
 void limit_check(const char* who, double ceiling_db, double lookahead_ms, double release_ms) {
-  if (!std::isfinite(ceiling_db) || !std::isfinite(lookahead_ms) || !std::isfinite(release_ms))
-    fail(std::string(who) + ": a value is not finite");
+  check_finite(who, {ceiling_db, lookahead_ms, release_ms});
   if (ceiling_db > 0.0) fail(std::string(who) + ": the ceiling must be <= 0 dB");
   if (lookahead_ms < 0.0 || lookahead_ms > 10.0) fail(std::string(who) + ": lookahead_ms must lie in 0 .. 10");
   if (release_ms < 0.0 || release_ms > 10000.0) fail(std::string(who) + ": release_ms must lie in 0 .. 10000");
@@ -29,7 +25,7 @@ void limit_check(const char* who, double ceiling_db, double lookahead_ms, double
 
 void master_check(const char* who, int sr, double target, double offset, double ceiling) {
   loud_check(who, sr, 2);
-  if (!std::isfinite(target) || !std::isfinite(offset)) fail(std::string(who) + ": a value is not finite");
+  check_finite(who, {target, offset});
   if (target > 0.0) fail(std::string(who) + ": target_lufs must be <= 0");
   limit_check(who, ceiling, 2.0, 100.0);
 }
@@ -39,33 +35,12 @@ float bits_float(uint32_t u) {
   std::memcpy(&f, &u, 4);
   return f;
 }
-// items per group: what the activation budget holds at the longest item's size (and RVCX_MAX_BATCH allows)
+// the group size at this item size, and the arena reserved for it (1 MiB beside the items for the small tables)
 int fx_group(Ctx* C, int B, size_t item_bytes) {
-  const char* cap = getenv("RVCX_MAX_BATCH");
-  const size_t most = cap ? (size_t)std::max(1, atoi(cap)) : (size_t)B;
-  const int G = (int)std::max<size_t>(1, std::min<size_t>(std::min<size_t>(most, (size_t)B), arena_budget(*C) / item_bytes));
+  const int G = fx_group_size(*C, B, item_bytes, 0);
   C->arena.reset();
   C->arena.reserve(item_bytes * G + ((size_t)1 << 20));
   return G;
-}
-
-void items_check(const char* who, int B, const void* const* x, const int64_t* n) {
-  if (B < 1 || !x || !n) fail(std::string(who) + ": null argument or B < 1");
-  for (int b = 0; b < B; ++b) {
-    if (!x[b]) fail(std::string(who) + ": null pointer in a table");
-    if (n[b] < 1 || n[b] > (int64_t)1 << 30) fail(std::string(who) + ": every item needs 1 .. 2^30 frames");
-  }
-}
-
-template <typename F>
-int host_call(F&& body) {
-  try {
-    body();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
 }
 
 }  // namespace
@@ -78,30 +53,25 @@ int rvcx_fx_loudness(rvcx_ctx* ctx, int B, const float* const* x, const int64_t*
                      double* tp_db, float* const* momentary) {
   API_BEGIN(ctx)
   loud_check("fx_loudness", sr, channels);
-  items_check("fx_loudness", B, reinterpret_cast<const void* const*>(x), n);
+  check_items("fx_loudness", B, x, n);
   if (!lufs) fail("fx_loudness: null argument");
-  int64_t n_max = 0;
-  for (int b = 0; b < B; ++b) {
-    n_max = std::max(n_max, n[b]);
+  for (int b = 0; b < B; ++b)
     if (momentary && fx_momentary_len((long)n[b], sr) > 0 && !momentary[b]) fail("fx_loudness: null pointer in a table");
-  }
   const int Cc = channels;
-  const long ld_max = fx_ld(n_max);
+  const long ld_max = fx_ld(*std::max_element(n, n + B));
   const size_t item = (size_t)ld_max * Cc * 8 + fx_loudness_scratch_bytes(1, Cc, ld_max, sr) + (size_t)(ld_max / (sr / 10) + 1) * 4 + 8192;
   const int G = fx_group(C, B, item);
   Arena& A = C->arena;
   hipStream_t s = C->stream;
-  C->timer.make();
-  hipEvent_t* ev = C->timer.ev;
-  float ms[9] = {0};
+  FxTimer T(*C);
   std::vector<double> L((size_t)B);
   std::vector<uint32_t> pk((size_t)B, 0);
   std::vector<std::vector<float>> mom((size_t)B);
   const FxKWeight kw = fx_kweight(sr);
-  for (int g0 = 0; g0 < B; g0 += G) {
+  int groups = 0;
+  for (int g0 = 0; g0 < B; g0 += G, ++groups) {
     const int Bg = std::min(G, B - g0), R = Bg * Cc;
-    long ld = 0;
-    for (int b = 0; b < Bg; ++b) ld = std::max(ld, fx_ld(n[g0 + b]));
+    const long ld = fx_ld(*std::max_element(n + g0, n + g0 + Bg));
     const size_t plane = (size_t)R * ld;
     const long mom_ld = fx_momentary_len(ld, sr) + 1;
     A.reset();
@@ -111,18 +81,14 @@ int rvcx_fx_loudness(rvcx_ctx* ctx, int B, const float* const* x, const int64_t*
     double* dl = A.alloc<double>((size_t)Bg);
     uint32_t* dpk = A.alloc<uint32_t>((size_t)Bg);
     float* dmom = momentary ? A.alloc<float>((size_t)Bg * mom_ld) : nullptr;
-    int* dlen = A.alloc<int>((size_t)R);
-    std::vector<int> len((size_t)R);
-    for (int r = 0; r < R; ++r) len[r] = (int)n[g0 + r / Cc];
-    RVCX_HIP(hipEventRecord(ev[0], s));
-    RVCX_HIP(hipMemcpyAsync(dlen, len.data(), (size_t)R * sizeof(int), hipMemcpyHostToDevice, s));
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * Cc, x[g0 + b], (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    launch_fx_deinterleave(stage, rows, dlen, Bg, Cc, ld, s);
-    RVCX_HIP(hipEventRecord(ev[1], s));
-    launch_fx_loudness(kw, rows, dlen, Bg, Cc, ld, sr, scratch, dl, dmom, mom_ld, s, ev + 2);
+    const std::vector<int> len = row_lengths(n + g0, Bg, Cc);
+    T.mark(0);
+    const int* dlen = to_dev(*C, len.data(), len.size());
+    stage_in([&](int b) { return std::make_pair(x[g0 + b], n[g0 + b]); }, Bg, Cc, ld, stage, rows, dlen, s);
+    T.mark(1);
+    launch_fx_loudness(kw, rows, dlen, Bg, Cc, ld, sr, scratch, dl, dmom, mom_ld, s, T.ev + 2);
     if (tp_db) launch_fx_truepeak(rows, dlen, Bg, Cc, ld, nullptr, dpk, s);
-    RVCX_HIP(hipEventRecord(ev[6], s));
+    T.mark(6);
     RVCX_HIP(hipMemcpyAsync(L.data() + g0, dl, (size_t)Bg * sizeof(double), hipMemcpyDeviceToHost, s));
     if (tp_db) RVCX_HIP(hipMemcpyAsync(pk.data() + g0, dpk, (size_t)Bg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     if (momentary)
@@ -131,15 +97,10 @@ int rvcx_fx_loudness(rvcx_ctx* ctx, int B, const float* const* x, const int64_t*
         mom[g0 + b].resize((size_t)nb);
         if (nb) RVCX_HIP(hipMemcpyAsync(mom[g0 + b].data(), dmom + (size_t)b * mom_ld, (size_t)nb * 4, hipMemcpyDeviceToHost, s));
       }
-    RVCX_HIP(hipEventRecord(ev[7], s));
+    T.mark(7);
     RVCX_HIP(hipStreamSynchronize(s));
-    float t = 0.f;
-    for (int k = 0; k < 7; ++k) {               // {copies + layout, local, carry, apply + energy, gates, true peak, copies back}
-      RVCX_HIP(hipEventElapsedTime(&t, ev[k], ev[k + 1]));
-      ms[k] += t;
-    }
-    RVCX_HIP(hipEventElapsedTime(&t, ev[0], ev[7]));
-    ms[8] += t;
+    // {copies + layout, local, carry, apply + energy, gates, true peak, copies back, -, total}
+    T.add_each(0, 0, 7), T.add(8, 0, 7);
   }
   A.reset();
   // everything is in: the caller's memory is written only now
@@ -148,15 +109,15 @@ int rvcx_fx_loudness(rvcx_ctx* ctx, int B, const float* const* x, const int64_t*
     if (tp_db) tp_db[b] = fx_db20(bits_float(pk[b]));
     if (momentary && !mom[b].empty()) RVCX_HIP(hipMemcpy(momentary[b], mom[b].data(), mom[b].size() * 4, hipMemcpyDefault));
   }
-  std::copy(ms, ms + 9, C->timing);
+  T.store(*C);
+  ctx->fx_groups = groups;
   API_END
 }
 
 int rvcx_op_fx_truepeak(rvcx_ctx* ctx, const float* x, int64_t n, int channels, float* p_out, double* tp_db) {
   API_BEGIN(ctx)
   loud_check("op_fx_truepeak", 48000, channels);
-  const void* xv = x;
-  items_check("op_fx_truepeak", 1, &xv, &n);
+  check_items("op_fx_truepeak", 1, &x, &n);
   if (!tp_db) fail("op_fx_truepeak: null argument");
   const long ld = fx_ld(n);
   const int Cc = channels;
@@ -168,11 +129,9 @@ int rvcx_op_fx_truepeak(rvcx_ctx* ctx, const float* x, int64_t n, int channels, 
   float* rows = A.alloc<float>((size_t)ld * Cc);
   float* p = A.alloc<float>((size_t)ld);
   uint32_t* dpk = A.alloc<uint32_t>(1);
-  int* dlen = A.alloc<int>(2);
   const int len[2] = {(int)n, (int)n};
-  RVCX_HIP(hipMemcpyAsync(dlen, len, 2 * sizeof(int), hipMemcpyHostToDevice, s));
-  RVCX_HIP(hipMemcpyAsync(stage, x, (size_t)n * Cc * 4, hipMemcpyDefault, s));
-  launch_fx_deinterleave(stage, rows, dlen, 1, Cc, ld, s);
+  const int* dlen = to_dev(*C, len, 2);
+  stage_in([&](int) { return std::make_pair(x, n); }, 1, Cc, ld, stage, rows, dlen, s);
   launch_fx_truepeak(rows, dlen, 1, Cc, ld, p, dpk, s);
   uint32_t pk = 0;
   RVCX_HIP(hipMemcpyAsync(&pk, dpk, sizeof(pk), hipMemcpyDeviceToHost, s));
@@ -188,8 +147,7 @@ int rvcx_op_fx_limit(rvcx_ctx* ctx, const float* x, int64_t n, int channels, int
   API_BEGIN(ctx)
   loud_check("op_fx_limit", sr, channels);
   limit_check("op_fx_limit", ceiling_db, lookahead_ms, release_ms);
-  const void* xv = x;
-  items_check("op_fx_limit", 1, &xv, &n);
+  check_items("op_fx_limit", 1, &x, &n);
   if (!y) fail("op_fx_limit: null argument");
   const long ld = fx_ld(n);
   const int Cc = channels;
@@ -206,11 +164,9 @@ int rvcx_op_fx_limit(rvcx_ctx* ctx, const float* x, int64_t n, int channels, int
   float* sg = A.alloc<float>((size_t)ld);
   float* state = A.alloc<float>(3 * nch + 64);
   uint32_t* dpk = A.alloc<uint32_t>(2);
-  int* dlen = A.alloc<int>(2);
   const int len[2] = {(int)n, (int)n};
-  RVCX_HIP(hipMemcpyAsync(dlen, len, 2 * sizeof(int), hipMemcpyHostToDevice, s));
-  RVCX_HIP(hipMemcpyAsync(stage, x, (size_t)n * Cc * 4, hipMemcpyDefault, s));
-  launch_fx_deinterleave(stage, rows, dlen, 1, Cc, ld, s);
+  const int* dlen = to_dev(*C, len, 2);
+  stage_in([&](int) { return std::make_pair(x, n); }, 1, Cc, ld, stage, rows, dlen, s);
   launch_fx_truepeak(rows, dlen, 1, Cc, ld, p, dpk, s);
   uint32_t pk = 0;
   RVCX_HIP(hipMemcpyAsync(&pk, dpk, sizeof(pk), hipMemcpyDeviceToHost, s));
@@ -240,22 +196,18 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
                    int16_t* const* out, double* report7) {
   API_BEGIN(ctx)
   master_check("fx_master", sr, target_lufs, vocal_offset_lu, ceiling_dbtp);
-  items_check("fx_master", B, reinterpret_cast<const void* const*>(vocal), n_v);
+  check_items("fx_master", B, vocal, n_v);
   if (!inst || !n_i || !out) fail("fx_master: null argument");
-  int64_t n_max = 0;
   for (int b = 0; b < B; ++b) {
     if (n_i[b] < 0 || n_i[b] > (int64_t)1 << 30) fail("fx_master: an instrumental needs 0 .. 2^30 frames");
     if ((n_i[b] && !inst[b]) || !out[b]) fail("fx_master: null pointer in a table");
-    n_max = std::max(n_max, n_v[b]);
   }
-  const long ld_max = fx_ld(n_max);
+  const long ld_max = fx_ld(*std::max_element(n_v, n_v + B));
   const size_t item = (size_t)ld_max * 56 + fx_loudness_scratch_bytes(1, 2, ld_max, sr) + (size_t)(ld_max / kFxChunk) * 12 + 8192;
   const int G = fx_group(C, B, item);
   Arena& A = C->arena;
   hipStream_t s = C->stream;
-  C->timer.make();
-  hipEvent_t* ev = C->timer.ev;
-  float ms[9] = {0};
+  FxTimer T(*C);
   const FxKWeight kw = fx_kweight(sr);
   const float c = (float)std::pow(10.0, ceiling_dbtp / 20.0), c_rel = fx_cte(100.0, sr);
   const int W = fx_lookahead(sr, 2.0);
@@ -264,8 +216,7 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
   int groups = 0;
   for (int g0 = 0; g0 < B; g0 += G, ++groups) {
     const int Bg = std::min(G, B - g0), R = Bg * 2;
-    long ld = 0;
-    for (int b = 0; b < Bg; ++b) ld = std::max(ld, fx_ld(n_v[g0 + b]));
+    const long ld = fx_ld(*std::max_element(n_v + g0, n_v + g0 + Bg));
     const size_t plane = (size_t)R * ld, nch = (size_t)(ld / kFxChunk);
     A.reset();
     float* stage = A.alloc<float>(plane);
@@ -281,9 +232,7 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
     double* dl = A.alloc<double>((size_t)Bg * 2);
     uint32_t* dpk = A.alloc<uint32_t>((size_t)Bg * 2);
     float* dg = A.alloc<float>((size_t)Bg * 2);
-    int* dlen = A.alloc<int>((size_t)R * 2 + Bg);
-    int *dlen_v = dlen, *dlen_i = dlen + R, *dilen = dlen + 2 * R;
-    std::vector<int> len((size_t)R * 2 + Bg);
+    std::vector<int> len((size_t)R * 2 + Bg);       // the vocals' rows, the instrumentals' rows (cut to their vocal), the items
     for (int b = 0; b < Bg; ++b) {
       const int nv = (int)n_v[g0 + b], ni = (int)std::min(n_i[g0 + b], n_v[g0 + b]);
       len[2 * b] = len[2 * b + 1] = nv, len[R + 2 * b] = len[R + 2 * b + 1] = ni, len[2 * R + b] = nv;
@@ -291,20 +240,17 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
     std::vector<double> L((size_t)Bg * 2), Lm((size_t)Bg), Lr((size_t)Bg);
     std::vector<float> gains((size_t)Bg * 2), gm((size_t)Bg);
     std::vector<uint32_t> pk((size_t)Bg * 2), low((size_t)Bg, 0x3f800000u);
-    RVCX_HIP(hipEventRecord(ev[0], s));
-    RVCX_HIP(hipMemcpyAsync(dlen, len.data(), len.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * 2, vocal[g0 + b], (size_t)len[2 * b] * 8, hipMemcpyDefault, s));
-    launch_fx_deinterleave(stage, V, dlen_v, Bg, 2, ld, s);
-    for (int b = 0; b < Bg; ++b)
-      if (len[R + 2 * b])
-        RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * 2, inst[g0 + b], (size_t)len[R + 2 * b] * 8, hipMemcpyDefault, s));
-    launch_fx_deinterleave(stage, I, dlen_i, Bg, 2, ld, s);
-    RVCX_HIP(hipEventRecord(ev[1], s));
+    T.mark(0);
+    const int* dlen_v = to_dev(*C, len.data(), len.size());
+    const int *dlen_i = dlen_v + R, *dilen = dlen_v + 2 * R;
+    // both stems pass through the one staging buffer (stream order); an empty instrumental copies nothing and has no frames to read
+    stage_in([&](int b) { return std::make_pair(vocal[g0 + b], n_v[g0 + b]); }, Bg, 2, ld, stage, V, dlen_v, s);
+    stage_in([&](int b) { return std::make_pair(inst[g0 + b], (int64_t)len[R + 2 * b]); }, Bg, 2, ld, stage, I, dlen_i, s);
+    T.mark(1);
     // the stems
     launch_fx_loudness(kw, V, dlen_v, Bg, 2, ld, sr, scratch, dl, nullptr, 0, s, nullptr);
     launch_fx_loudness(kw, I, dlen_i, Bg, 2, ld, sr, scratch, dl + Bg, nullptr, 0, s, nullptr);
-    RVCX_HIP(hipEventRecord(ev[2], s));
+    T.mark(2);
     RVCX_HIP(hipMemcpyAsync(L.data(), dl, L.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     RVCX_HIP(hipStreamSynchronize(s));      // the gains are formed on the host in double, as the host twin forms them
     for (int b = 0; b < Bg; ++b) {
@@ -313,16 +259,16 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
     }
     RVCX_HIP(hipMemcpyAsync(dg, gains.data(), gains.size() * sizeof(float), hipMemcpyHostToDevice, s));
     launch_fx_master_mix(V, I, dlen_v, dlen_i, dg, dg + Bg, Bg, 2, ld, s);
-    RVCX_HIP(hipEventRecord(ev[3], s));
+    T.mark(3);
     launch_fx_loudness(kw, V, dlen_v, Bg, 2, ld, sr, scratch, dl, nullptr, 0, s, nullptr);
-    RVCX_HIP(hipEventRecord(ev[4], s));
+    T.mark(4);
     RVCX_HIP(hipMemcpyAsync(Lm.data(), dl, Lm.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     RVCX_HIP(hipStreamSynchronize(s));
     for (int b = 0; b < Bg; ++b) gm[b] = (float)fx_gain_to(target_lufs, Lm[b]);
     RVCX_HIP(hipMemcpyAsync(dg, gm.data(), gm.size() * sizeof(float), hipMemcpyHostToDevice, s));
     launch_fx_scale(V, dg, Bg, 2, ld, s);
     launch_fx_truepeak(V, dlen_v, Bg, 2, ld, p, dpk, s);
-    RVCX_HIP(hipEventRecord(ev[5], s));
+    T.mark(5);
     RVCX_HIP(hipMemcpyAsync(pk.data(), dpk, (size_t)Bg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     RVCX_HIP(hipStreamSynchronize(s));      // the skip decision needs the peaks
     bool over = false;
@@ -331,41 +277,32 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
       ctx->fx_passes[0] = launch_fx_limit_gain(p, dilen, len.data() + 2 * R, Bg, ld, c, W, c_rel, u, e, state, sg, dpk + Bg, s);
       RVCX_HIP(hipMemcpyAsync(low.data(), dpk + Bg, (size_t)Bg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     }
-    RVCX_HIP(hipEventRecord(ev[6], s));
+    T.mark(6);
     launch_fx_limit_apply(V, over ? sg : nullptr, dlen_v, Bg, 2, ld, V, nullptr, pcm, s);
-    RVCX_HIP(hipEventRecord(ev[7], s));
+    T.mark(7);
     launch_fx_loudness(kw, V, dlen_v, Bg, 2, ld, sr, scratch, dl, nullptr, 0, s, nullptr);
     launch_fx_truepeak(V, dlen_v, Bg, 2, ld, nullptr, dpk, s);
-    RVCX_HIP(hipEventRecord(ev[8], s));
+    T.mark(8);
     RVCX_HIP(hipMemcpyAsync(Lr.data(), dl, Lr.size() * sizeof(double), hipMemcpyDeviceToHost, s));
     RVCX_HIP(hipMemcpyAsync(pk.data() + Bg, dpk, (size_t)Bg * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
     for (int b = 0; b < Bg; ++b) {
       pcm_host[g0 + b].resize((size_t)len[2 * b] * 2);
       RVCX_HIP(hipMemcpyAsync(pcm_host[g0 + b].data(), pcm + (size_t)b * ld * 2, (size_t)len[2 * b] * 4, hipMemcpyDeviceToHost, s));
     }
-    RVCX_HIP(hipEventRecord(ev[9], s));
+    T.mark(9);
     RVCX_HIP(hipStreamSynchronize(s));
     for (int b = 0; b < Bg; ++b) {
       double* r = rep.data() + (size_t)(g0 + b) * 7;
       r[0] = L[b], r[1] = L[Bg + b], r[2] = Lm[b], r[3] = Lr[b], r[4] = fx_db20(bits_float(pk[b])), r[5] = fx_db20(bits_float(pk[Bg + b]));
       r[6] = (double)bits_float(low[b]);
     }
-    float t = 0.f;
-    for (int k = 0; k < 7; ++k) {   // {stems, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters}
-      RVCX_HIP(hipEventElapsedTime(&t, ev[k + 1], ev[k + 2]));
-      ms[k] += t;
-    }
-    RVCX_HIP(hipEventElapsedTime(&t, ev[0], ev[1]));
-    ms[7] += t;
-    RVCX_HIP(hipEventElapsedTime(&t, ev[8], ev[9]));
-    ms[7] += t;
-    RVCX_HIP(hipEventElapsedTime(&t, ev[0], ev[9]));
-    ms[8] += t;
+    // {stems, mix, mix loudness, scale + true peak, limiter gain, gain + int16, result meters, copies at either end, total}
+    T.add_each(0, 1, 7), T.add(7, 0, 1), T.add(7, 8, 9), T.add(8, 0, 9);
   }
   A.reset();
   for (int b = 0; b < B; ++b) RVCX_HIP(hipMemcpy(out[b], pcm_host[b].data(), pcm_host[b].size() * 2, hipMemcpyDefault));
   if (report7) std::copy(rep.begin(), rep.end(), report7);
-  std::copy(ms, ms + 9, C->timing);
+  T.store(*C);
   ctx->fx_groups = groups;
   API_END
 }
@@ -374,7 +311,7 @@ int rvcx_fx_master(rvcx_ctx* ctx, int B, const float* const* vocal, const int64_
 int rvcx_fx_kweight_coeffs(int sr, double* coef10) {
   return host_call([&] {
     if (!coef10) fail("fx_kweight_coeffs: null pointer");
-    if (!fx_rate_ok(sr)) fail("fx_kweight_coeffs: the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
+    check_rate("fx_kweight_coeffs", sr);
     const FxKWeight k = fx_kweight(sr);
     const double v[10] = {k.sb0, k.sb1, k.sb2, k.sa1, k.sa2, k.hb0, k.hb1, k.hb2, k.ha1, k.ha2};
     std::copy(v, v + 10, coef10);

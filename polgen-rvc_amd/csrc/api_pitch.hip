@@ -1,7 +1,5 @@
 // C ABI of librvcx.so (include/rvcx.h): time stretch and pitch shift (stages 13 and 14), their taps and their host twins.
-#include "api_internal.h"
-#include "effects.h"
-#include "pitch.h"
+#include "api_fx_common.h"
 
 // A2 of rvcx_fx_stretch_own_host is written out rounding by rounding, as in pitch.hip
 #pragma clang fp contract(off)
@@ -16,28 +14,18 @@ int g_chunk_frames = 0, g_segment_frames = 0;      // rvcx_fx_stretch_override; 
 int chunk_frames() { return g_chunk_frames > 0 ? g_chunk_frames : kStretchChunk; }
 int segment_frames() { return g_segment_frames > 0 ? g_segment_frames : kStretchSegment; }
 
-long pad256(long n) { return (std::max<long>(n, 1) + 255) / 256 * 256; }
-
 void stretch_check(const char* who, int sr, int channels, int64_t P, int64_t Q) {
-  if (!fx_rate_ok(sr)) fail(std::string(who) + ": the sample rate must be a multiple of 100 Hz within 8000 .. 192000");
-  if (channels != 1 && channels != 2) fail(std::string(who) + ": channels must be 1 or 2");
+  check_rate(who, sr);
+  check_channels(who, channels);
   if (!fx_stretch_ratio_ok((long)P, (long)Q)) fail(std::string(who) + ": 1 <= Q <= 2^20 and Q / 2 <= P <= 2 Q are required");
 }
 
 long pitch_check(const char* who, int sr, int channels, double semitones) {
-  if (!std::isfinite(semitones)) fail(std::string(who) + ": a value is not finite");
+  check_finite(who, {semitones});
   if (std::fabs(semitones) > 12.0) fail(std::string(who) + ": semitones must lie in -12 .. 12");
   const long P = fx_pitch_P(sr > 0 ? sr : 1, semitones);
   stretch_check(who, sr, channels, P, sr);
   return P;
-}
-
-void items_check(const char* who, int B, const void* const* x, const int64_t* n, const void* const* y) {
-  if (B < 1 || !x || !n || !y) fail(std::string(who) + ": null argument or B < 1");
-  for (int b = 0; b < B; ++b) {
-    if (!x[b] || !y[b]) fail(std::string(who) + ": null pointer in a table");
-    if (n[b] < 1 || n[b] > (int64_t)1 << 30) fail(std::string(who) + ": every item needs 1 .. 2^30 frames");
-  }
 }
 
 // the int lengths of the device rows hold the stretched item too
@@ -74,52 +62,34 @@ void run_stretch(rvcx_ctx* ctx, Ctx* C, int B, const float* const* x, const int6
                  bool pitch, float* const* y, const StretchTaps& taps) {
   const FxStretchGeom g = fx_stretch_geom(sr);
   const int S = segment_frames(), Lc = std::min(chunk_frames(), S);
-  int64_t n_max = 0;
-  for (int b = 0; b < B; ++b) n_max = std::max(n_max, n[b]);
   const size_t table_bytes = (size_t)g.N * 8 + (pitch ? resample_table_doubles(0) * 8 : 0) + ((size_t)1 << 20);
   auto item_bytes = [&](long n_long) {
     const long ld = pad256(n_long), lds = pad256(fx_stretch_len(n_long, P, Q)), Tf = fx_stretch_T(n_long, g.H) + 2;
     return (size_t)Cc * ((size_t)std::max(ld, lds) * 4 + (size_t)ld * 8 + (size_t)lds * 4 +
                          fx_stretch_row_bytes(g, Tf, S, Lc, taps.D != nullptr) + 16 * 256 + 64);
   };
-  const char* cap = getenv("RVCX_MAX_BATCH");
-  const size_t most = cap ? (size_t)std::max(1, atoi(cap)) : (size_t)B;
-  const size_t budget = arena_budget(*C);
-  const int G = (int)std::max<size_t>(
-      1, std::min<size_t>(std::min<size_t>(most, (size_t)B), (budget > table_bytes ? budget - table_bytes : 0) / item_bytes(n_max)));
+  const size_t worst = item_bytes((long)*std::max_element(n, n + B));
+  const int G = fx_group_size(*C, B, worst, table_bytes);
   Arena& A = C->arena;
   A.reset();
-  A.reserve(item_bytes(n_max) * G + table_bytes);
+  A.reserve(worst * G + table_bytes);
   hipStream_t s = C->stream;
-  C->timer.make();
-  hipEvent_t* ev = C->timer.ev;
-  float ms[9] = {0};
-  auto add = [&](int slot, hipEvent_t a, hipEvent_t b) {
-    float t = 0.f;
-    RVCX_HIP(hipEventElapsedTime(&t, a, b));
-    ms[slot] += t;
-  };
-  std::vector<float> w;
-  std::vector<float2> tw;
-  fx_stretch_tables(g.N, w, tw);
+  FxTimer T(*C);
+  const StftTables tables(g.N);
   int groups = 0;
   for (int g0 = 0; g0 < B; g0 += G, ++groups) {
     const int Bg = std::min(G, B - g0), R = Bg * Cc;
-    long nmax = 0;
-    for (int b = 0; b < Bg; ++b) nmax = std::max<long>(nmax, (long)n[g0 + b]);
+    const long nmax = (long)*std::max_element(n + g0, n + g0 + Bg);
     const long ld = pad256(nmax), lds = pad256(fx_stretch_len(nmax, P, Q)), ldm = std::max(ld, lds);
     const long Tmax = fx_stretch_T(nmax, g.H), Jmax = fx_stretch_J(Tmax, P, Q);
     const int nch = (S + Lc - 1) / Lc;
     const size_t nb = (size_t)g.nb;
     A.reset();
-    float* dw = A.alloc<float>((size_t)g.N);
-    float2* dtw = A.alloc<float2>((size_t)g.N / 2);
-    RVCX_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
-    RVCX_HIP(hipMemcpyAsync(dtw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice, s));
+    FxStretchDev d{};
+    tables.upload(*C, d.w, d.tw);
     ResampleFilter rf;
     if (pitch) rf = make_resample_filter(A, (int)P, sr, s, 0);
-    FxStretchDev d{};
-    d.g = g, d.P = P, d.Q = Q, d.R = R, d.ld = ld, d.Tf = Tmax + 2, d.S = S, d.Lc = Lc, d.w = dw, d.tw = dtw;
+    d.g = g, d.P = P, d.Q = Q, d.R = R, d.ld = ld, d.Tf = Tmax + 2, d.S = S, d.Lc = Lc;
     float* stage = A.alloc<float>((size_t)Bg * Cc * ldm);
     float* rows = A.alloc<float>((size_t)R * ld);
     float* ys = A.alloc<float>((size_t)R * lds);
@@ -136,21 +106,14 @@ void run_stretch(rvcx_ctx* ctx, Ctx* C, int B, const float* const* x, const int6
     d.Rstart = A.alloc<uint32_t>((size_t)R * (nch + 1) * nb);
     d.fr = A.alloc<float>((size_t)R * (S + 3) * g.N);
     d.tmp3 = A.alloc<float>((size_t)R * 3 * g.N);
-    int* dlen = A.alloc<int>((size_t)R * 2);
-    d.len = dlen;
-    std::vector<int> len((size_t)R * 2);
-    for (int r = 0; r < R; ++r) {
-      len[r] = (int)n[g0 + r / Cc];
-      len[R + r] = pitch ? len[r] : (int)fx_stretch_len(len[r], P, Q);
-    }
-    RVCX_HIP(hipEventRecord(ev[0], s));
-    RVCX_HIP(hipMemcpyAsync(dlen, len.data(), len.size() * sizeof(int), hipMemcpyHostToDevice, s));
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(stage + (size_t)b * ld * Cc, x[g0 + b], (size_t)n[g0 + b] * Cc * 4, hipMemcpyDefault, s));
-    launch_fx_deinterleave(stage, rows, dlen, Bg, Cc, ld, s);
+    std::vector<int> len = row_lengths(n + g0, Bg, Cc);       // the R rows as they come, then the R rows as they leave
+    for (int r = 0; r < R; ++r) len.push_back(pitch ? len[r] : (int)fx_stretch_len(len[r], P, Q));
+    T.mark(0);
+    const int* dlen = d.len = to_dev(*C, len.data(), len.size());
+    stage_in([&](int b) { return std::make_pair(x[g0 + b], n[g0 + b]); }, Bg, Cc, ld, stage, rows, dlen, s);
     RVCX_HIP(hipMemsetAsync(d.Rcarry, 0, (size_t)R * nb * 4, s));           // R_0 = 0
-    RVCX_HIP(hipEventRecord(ev[1], s));
-    launch_stretch_analysis(d, rows, s, ev + 2);
+    T.mark(1);
+    launch_stretch_analysis(d, rows, s, T.ev + 2);
     if (taps.any()) {
       const size_t cnt = (size_t)(fx_stretch_T(len[0], g.H) + 2) * nb;       // taps: one row
       if (taps.D) RVCX_HIP(hipMemcpyAsync(taps.D, d.D, cnt * 8, hipMemcpyDefault, s));
@@ -168,7 +131,7 @@ void run_stretch(rvcx_ctx* ctx, Ctx* C, int B, const float* const* x, const int6
         RVCX_HIP(hipMemcpyAsync(taps.R + (size_t)s0 * nb, d.Rseg, (size_t)(j1 - s0) * nb * 4, hipMemcpyDefault, s));
       }
     }
-    RVCX_HIP(hipEventRecord(ev[8], s));
+    T.mark(8);
     const float* res = ys;
     long ldo = lds;
     if (pitch) {
@@ -180,51 +143,36 @@ void run_stretch(rvcx_ctx* ctx, Ctx* C, int B, const float* const* x, const int6
       }
       res = yo, ldo = ld;
     }
-    RVCX_HIP(hipEventRecord(ev[9], s));
-    launch_fx_interleave(res, stage, dlen + R, Bg, Cc, ldo, s);
-    for (int b = 0; b < Bg; ++b)
-      RVCX_HIP(hipMemcpyAsync(y[g0 + b], stage + (size_t)b * ldo * Cc, (size_t)len[R + b * Cc] * Cc * 4, hipMemcpyDefault, s));
-    RVCX_HIP(hipEventRecord(ev[10], s));
+    T.mark(9);
+    stage_out(res, dlen + R, Bg, Cc, ldo, stage, s, [&](int b) { return std::make_pair(y[g0 + b], (int64_t)len[R + b * Cc]); });
+    T.mark(10);
     RVCX_HIP(hipStreamSynchronize(s));
-    add(0, ev[0], ev[1]), add(1, ev[1], ev[2]), add(2, ev[2], ev[3]);
+    // {copies in, transforms, owners, scan, inverse transforms, overlap-add, resampler, copies out, total}
+    T.add_each(0, 0, 3);
     for (size_t k = 0; k + 3 < pool.ev.size(); k += 4)
-      add(3, pool.ev[k], pool.ev[k + 1]), add(4, pool.ev[k + 1], pool.ev[k + 2]), add(5, pool.ev[k + 2], pool.ev[k + 3]);
-    add(6, ev[8], ev[9]), add(7, ev[9], ev[10]), add(8, ev[0], ev[10]);
+      T.add(3, pool.ev[k], pool.ev[k + 1]), T.add(4, pool.ev[k + 1], pool.ev[k + 2]), T.add(5, pool.ev[k + 2], pool.ev[k + 3]);
+    T.add(6, 8, 9), T.add(7, 9, 10), T.add(8, 0, 10);
   }
   A.reset();
-  std::copy(ms, ms + 9, C->timing);      // {copies in, transforms, owners, scan, inverse transforms, overlap-add, resampler, copies out, total}
+  T.store(*C);
   ctx->fx_groups = groups;
-}
-
-template <typename F>
-int host_call(F&& body) {
-  try {
-    body();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
 }
 
 void host_stretch(const char* who, const float* x, int64_t n, int channels, int sr, long P, long Q, bool pitch, float* y,
                   const StretchTaps& taps) {
   if (!x || !y) fail(std::string(who) + ": null pointer");
-  if (n < 1 || n > (int64_t)1 << 30) fail(std::string(who) + ": 1 .. 2^30 frames are required");
+  check_frames(who, n, "1 .. 2^30 frames are required");
   if (taps.any() && channels != 1) fail(std::string(who) + ": the taps take one channel");
   out_len_check(who, 1, &n, P, Q);
   const long ns = fx_stretch_len((long)n, P, Q), no = pitch ? (long)n : ns;
-  std::vector<float> plane((size_t)n), st((size_t)std::max<long>(ns, 1)), out((size_t)no);
-  for (int c = 0; c < channels; ++c) {
-    for (long i = 0; i < n; ++i) plane[i] = x[i * channels + c];
-    fx_stretch_host(plane.data(), (long)n, sr, P, Q, st.data(), taps.D, taps.own, taps.TH, taps.R);
-    if (pitch) {
-      std::fill(out.begin(), out.end(), 0.f);
-      resample_plane_host((int)P, sr, st.data(), ns, out.data(), std::min<long>(resample_out_len(ns, (int)P, sr), (long)n));
-    }
-    const float* res = pitch ? out.data() : st.data();
-    for (long i = 0; i < no; ++i) y[i * channels + c] = res[i];
-  }
+  std::vector<float> st((size_t)std::max<long>(ns, 1)), out((size_t)(pitch ? no : 0));
+  host_planes(x, n, channels, y, no, [&](int, const float* plane) -> const float* {
+    fx_stretch_host(plane, (long)n, sr, P, Q, st.data(), taps.D, taps.own, taps.TH, taps.R);
+    if (!pitch) return st.data();
+    std::fill(out.begin(), out.end(), 0.f);
+    resample_plane_host((int)P, sr, st.data(), ns, out.data(), std::min<long>(resample_out_len(ns, (int)P, sr), (long)n));
+    return out.data();
+  });
 }
 
 }  // namespace
@@ -250,7 +198,7 @@ int64_t rvcx_fx_stretch_len(int64_t n, int64_t P, int64_t Q) {
 int rvcx_fx_stretch_frames(int64_t n, int sr, int64_t P, int64_t Q, int64_t* T, int64_t* J, int32_t* N) {
   return host_call([&] {
     stretch_check("fx_stretch_frames", sr, 1, P, Q);
-    if (n < 1 || n > (int64_t)1 << 30) fail("fx_stretch_frames: 1 .. 2^30 frames are required");
+    check_frames("fx_stretch_frames", n, "1 .. 2^30 frames are required");
     const FxStretchGeom g = fx_stretch_geom(sr);
     const long t = fx_stretch_T((long)n, g.H);
     if (T) *T = t;
@@ -267,7 +215,7 @@ int rvcx_fx_stretch(rvcx_ctx* ctx, int B, const float* const* x, const int64_t* 
                     float* const* y) {
   API_BEGIN(ctx)
   stretch_check("fx_stretch", sr, channels, P, Q);
-  items_check("fx_stretch", B, reinterpret_cast<const void* const*>(x), n, reinterpret_cast<const void* const*>(y));
+  check_items("fx_stretch", B, x, n, y);
   out_len_check("fx_stretch", B, n, (long)P, (long)Q);
   run_stretch(ctx, C, B, x, n, channels, sr, (long)P, (long)Q, false, y, StretchTaps{});
   API_END
@@ -277,14 +225,8 @@ int rvcx_fx_pitch_shift(rvcx_ctx* ctx, int B, const float* const* x, const int64
                         float* const* y) {
   API_BEGIN(ctx)
   const long P = pitch_check("fx_pitch_shift", sr, channels, semitones);
-  items_check("fx_pitch_shift", B, reinterpret_cast<const void* const*>(x), n, reinterpret_cast<const void* const*>(y));
-  if (P == sr) {                   // skip: nothing is launched, the output is the input bit for bit
-    for (int b = 0; b < B; ++b)
-      if (y[b] != x[b]) RVCX_HIP(hipMemcpy(y[b], x[b], (size_t)n[b] * channels * 4, hipMemcpyDefault));
-    std::fill(C->timing, C->timing + 9, 0.f);
-    ctx->fx_groups = 0;
-    return;
-  }
+  check_items("fx_pitch_shift", B, x, n, y);
+  if (P == sr) return fx_skip(ctx, B, x, n, channels, y);
   out_len_check("fx_pitch_shift", B, n, P, sr);
   run_stretch(ctx, C, B, x, n, channels, sr, P, sr, true, y, StretchTaps{});
   API_END
@@ -294,9 +236,7 @@ int rvcx_op_fx_stretch_taps(rvcx_ctx* ctx, const float* x, int64_t n, int sr, in
                             int32_t* own, uint32_t* TH, uint32_t* R) {
   API_BEGIN(ctx)
   stretch_check("op_fx_stretch_taps", sr, 1, P, Q);
-  const void* xv = x;
-  const void* yv = y;
-  items_check("op_fx_stretch_taps", 1, &xv, &n, &yv);
+  check_items("op_fx_stretch_taps", 1, &x, &n, &y);
   out_len_check("op_fx_stretch_taps", 1, &n, (long)P, (long)Q);
   StretchTaps t;
   t.D = D, t.own = own, t.TH = TH, t.R = R;
@@ -320,7 +260,7 @@ int rvcx_fx_pitch_shift_host(const float* x, int64_t n, int channels, int sr, do
   return host_call([&] {
     const long P = pitch_check("fx_pitch_shift_host", sr, channels, semitones);
     if (!x || !y) fail("fx_pitch_shift_host: null pointer");
-    if (n < 1 || n > (int64_t)1 << 30) fail("fx_pitch_shift_host: 1 .. 2^30 frames are required");
+    check_frames("fx_pitch_shift_host", n, "1 .. 2^30 frames are required");
     if (P == sr) {
       if (D || own || TH || R) fail("fx_pitch_shift_host: the stage is skipped at this shift, it has no taps");
       if (y != x) std::memcpy(y, x, (size_t)n * channels * 4);

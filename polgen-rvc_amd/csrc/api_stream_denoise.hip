@@ -1,8 +1,7 @@
 // C ABI of librvcx.so (include/rvcx.h "live noise reduction", stage 16): the causal spectral gate at either edge of a
 // live-stream session's step (rvcx_stream_open_dn, _set_denoise, _last_dn_ms; the step itself is api_stream.hip's), the same
 // gate without a session (rvcx_op_stream_denoise), its host twin and the delay rule.
-#include "api_internal.h"
-#include "denoise_live.h"
+#include "api_fx_common.h"
 
 using namespace rvcx;
 using namespace rvcx::api;
@@ -19,24 +18,18 @@ LivePlan live_check(const char* who_c, const rvcx_live_denoise_params* p, int sr
   const std::string who(who_c);
   if (!p) fail(who + ": null parameters");
   if (p->sample_rate != 0 && p->sample_rate != sr) fail(who + ": sample_rate must be 0 or the rate of the signal, " + std::to_string(sr));
-  if (!dn_live_rate_ok(sr)) fail(who + ": the sample rate must be a multiple of 100 Hz within 3200 .. 192000");
+  check_rate(who_c, sr, true);
   if (p->channels != 0 && p->channels != 1) fail(who + ": channels must be 0 or 1 (live noise reduction is mono)");
   if (p->mode != 0 && p->mode != 1) fail(who + ": mode must be 0 (profile) or 1 (adaptive)");
-  const float all[9] = {p->strength, p->n_std, p->knee_db, p->thresh_mult, p->slope, p->time_constant_s, p->fall_time_s,
-                        p->freq_smooth_hz, p->time_smooth_ms};
-  for (float f : all)
-    if (!std::isfinite(f)) fail(who + ": a value is not finite");
-  auto range = [&](float f, double lo, double hi, const char* name) {
-    if (!((double)f >= lo && (double)f <= hi))
-      fail(who + ": " + name + " must lie in " + std::to_string(lo) + " .. " + std::to_string(hi));
-  };
-  range(p->strength, 0.0, 1.0, "strength");
-  range(p->n_std, 0.0, 10.0, "n_std");
-  range(p->knee_db, (double)0.1f, 20.0, "knee_db");
-  range(p->thresh_mult, 0.0, 20.0, "thresh_mult");
-  range(p->slope, (double)0.1f, 100.0, "slope");
-  range(p->time_constant_s, (double)0.05f, 30.0, "time_constant_s");
-  range(p->fall_time_s, (double)0.01f, (double)p->time_constant_s, "fall_time_s (0.01 .. time_constant_s)");
+  check_finite(who_c, {p->strength, p->n_std, p->knee_db, p->thresh_mult, p->slope, p->time_constant_s, p->fall_time_s,
+                       p->freq_smooth_hz, p->time_smooth_ms});
+  check_range(who_c, p->strength, 0.0, 1.0, "strength");
+  check_range(who_c, p->n_std, 0.0, 10.0, "n_std");
+  check_range(who_c, p->knee_db, (double)0.1f, 20.0, "knee_db");
+  check_range(who_c, p->thresh_mult, 0.0, 20.0, "thresh_mult");
+  check_range(who_c, p->slope, (double)0.1f, 100.0, "slope");
+  check_range(who_c, p->time_constant_s, (double)0.05f, 30.0, "time_constant_s");
+  check_range(who_c, p->fall_time_s, (double)0.01f, (double)p->time_constant_s, "fall_time_s (0.01 .. time_constant_s)");
   if (p->freq_smooth_hz < 0.f || p->time_smooth_ms < 0.f) fail(who + ": freq_smooth_hz and time_smooth_ms must not be negative");
   LivePlan P;
   P.g = dn_live_geom(sr);
@@ -91,17 +84,6 @@ void profile_device(Ctx& c, const LivePlan& P, const float* w, const float2* tw,
   A.reset(mk);       // (stream order: whatever takes this memory next runs behind these launches)
 }
 
-template <typename F>
-int host_call(F&& body) {
-  try {
-    body();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
-}
-
 }  // namespace
 
 extern "C" {
@@ -111,7 +93,7 @@ int rvcx_stream_denoise_delay(int sr) { return dn_live_rate_ok(sr) ? dn_live_geo
 int rvcx_stream_denoise_frames(int64_t n, int sr, float freq_smooth_hz, float time_smooth_ms, int64_t* T, int32_t* N, int32_t* nf,
                                int32_t* nt) {
   return host_call([&] {
-    if (!dn_live_rate_ok(sr)) fail("stream_denoise_frames: the sample rate must be a multiple of 100 Hz within 3200 .. 192000");
+    check_rate("stream_denoise_frames", sr, true);
     if (n < 0 || n > (int64_t)1 << 40) fail("stream_denoise_frames: n out of range");
     if (!(freq_smooth_hz >= 0.f) || !(time_smooth_ms >= 0.f) || !std::isfinite(freq_smooth_hz) || !std::isfinite(time_smooth_ms))
       fail("stream_denoise_frames: the widths must be finite and not negative");
@@ -167,12 +149,10 @@ int rvcx_stream_open_dn(rvcx_ctx* ctx, int model_id, const rvcx_stream_cfg* cfg,
       RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&L.acc), (size_t)se.S * (N + L.B) * 4));
       RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&sd.stage), (size_t)se.S * L.B * 4));
       RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&sd.tables), (size_t)2 * N * 4));
-      std::vector<float> w;
-      std::vector<float2> tw;
-      fx_stretch_tables(N, w, tw);
-      RVCX_HIP(hipMemcpyAsync(sd.tables, w.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
-      RVCX_HIP(hipMemcpyAsync(sd.tables + N, tw.data(), (size_t)N / 2 * 8, hipMemcpyHostToDevice, s));
-      RVCX_HIP(hipStreamSynchronize(s));      // (w and tw are this scope's)
+      const StftTables tables(N);             // (into the session's own memory, not the arena)
+      RVCX_HIP(hipMemcpyAsync(sd.tables, tables.w.data(), (size_t)N * 4, hipMemcpyHostToDevice, s));
+      RVCX_HIP(hipMemcpyAsync(sd.tables + N, tables.tw.data(), (size_t)N / 2 * 8, hipMemcpyHostToDevice, s));
+      RVCX_HIP(hipStreamSynchronize(s));      // (the tables are this scope's)
       L.w = sd.tables, L.tw = reinterpret_cast<const float2*>(sd.tables + N);
       if (L.v.mode == 0) {
         RVCX_HIP(hipMalloc(reinterpret_cast<void**>(&sd.prof), (size_t)2 * nb * sizeof(double)));
@@ -230,7 +210,7 @@ int rvcx_fx_denoise_live_host(const float* x, int64_t n, int sr, const float* no
   return host_call([&] {
     const LivePlan P = live_check("fx_denoise_live_host", params, sr);
     if (!x || !y) fail("fx_denoise_live_host: null pointer");
-    if (n < 1 || n > (int64_t)1 << 30) fail("fx_denoise_live_host: 1 .. 2^30 samples are required");
+    check_frames("fx_denoise_live_host", n, "1 .. 2^30 samples are required");
     clip_check("fx_denoise_live_host", P, noise, n_noise);
     if (f && P.h.v.mode != 1) fail("fx_denoise_live_host: f exists in mode 1 only");
     std::vector<double> mu, sd;
@@ -266,18 +246,12 @@ int rvcx_op_stream_denoise(rvcx_ctx* ctx, const float* x, int S, int64_t frames,
   C->arena.reset();
   hipStream_t s = C->stream;
   Arena& A = C->arena;
-  std::vector<float> w;
-  std::vector<float2> tw;
-  fx_stretch_tables(P.g.N, w, tw);
-  float* dw = A.alloc<float>(w.size());
-  float2* dtw = A.alloc<float2>(tw.size());
-  RVCX_HIP(hipMemcpyAsync(dw, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
-  RVCX_HIP(hipMemcpyAsync(dtw, tw.data(), tw.size() * 8, hipMemcpyHostToDevice, s));
-  d.w = dw, d.tw = dtw;
+  const StftTables tables(P.g.N);
+  tables.upload(*C, d.w, d.tw);
   if (P.h.v.mode == 0) {
     double* mu = A.alloc<double>((size_t)P.g.nb);
     double* sd = A.alloc<double>((size_t)P.g.nb);
-    profile_device(*C, P, dw, dtw, noise, (long)n_noise, mu, sd);
+    profile_device(*C, P, d.w, d.tw, noise, (long)n_noise, mu, sd);
     d.mu = mu, d.sd = sd;
   }
   float* dx = to_dev(*C, x, nx);

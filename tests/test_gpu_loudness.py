@@ -4,7 +4,8 @@ the master against its host twin, and the mirror module end to end.
 
 Shapes: sr = 8000 (h = 800, a block is 3200 samples) with items of 1, 3199 (no block), 3200, 3999 (still one block), 4000 (two
 blocks), 16000 with 0.2 s of exact zeros in the middle and 4 chunks exactly, each mono and stereo, plus an all-zero item; 2 s
-at 44100, 48000 and 192000 Hz; EBU Tech 3341 cases 3 - 5 at 48 kHz."""
+at 44100, 48000 and 192000 Hz; EBU Tech 3341 cases 3 - 5 at 48 kHz; the master in one and in two groups on three stereo items of
+30000, 41000 and 24000 frames at 48 kHz (one instrumental empty, one longer than its vocal)."""
 import os
 
 import numpy as np
@@ -199,6 +200,30 @@ def test_master_equals_the_host_twin(ctx):
         ctx.fx_master(v, m, SR, 1.0)
     with pytest.raises(L.RvcxError):
         ctx.fx_master(v, m, SR, -16.0, ceiling_dbtp=0.5)
+
+
+def test_master_grouping_changes_no_bit(ctx, monkeypatch):
+    """Three stereo items at 48 kHz, one with an empty instrumental and one whose instrumental outlasts its vocal: as one
+    group, as two groups (RVCX_MAX_BATCH = 2) and item by item the int16 outputs and the seven report values are the same
+    bits, and rvcx_fx_last_passes reports the groups the call ran in."""
+    L = _L()
+    sr = 48000
+    v = [_signal(30000, sr, 80), _signal(41000, sr, 81, scale=0.9), _signal(24000, sr, 82)]
+    m = [_signal(30000, sr, 83, scale=0.2), np.zeros((0, 2), np.float32), _signal(37000, sr, 84, scale=0.7)]
+
+    def flat(outs, reps):
+        return [(o.tobytes(), np.array([r[k] for k in L.MASTER_REPORT], np.float64).tobytes()) for o, r in zip(outs, reps)]
+    monkeypatch.delenv("RVCX_MAX_BATCH", raising=False)
+    whole = flat(*ctx.fx_master(v, m, sr, -16.0, 1.0, -1.0))
+    assert ctx.fx_last_passes()[1] == 1
+    monkeypatch.setenv("RVCX_MAX_BATCH", "2")
+    grouped = flat(*ctx.fx_master(v, m, sr, -16.0, 1.0, -1.0))
+    assert ctx.fx_last_passes()[1] == 2
+    monkeypatch.delenv("RVCX_MAX_BATCH")
+    assert grouped == whole
+    for b in range(3):
+        assert flat(*ctx.fx_master([v[b]], [m[b]], sr, -16.0, 1.0, -1.0))[0] == whole[b], b
+    assert len(L.MASTER_REPORT) == 7 and len(whole[0][0]) == 30000 * 4
 
 
 # ---- the mirror module ---------------------------------------------------------------------------------------------------------
