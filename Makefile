@@ -53,6 +53,15 @@ build/asan/formant_main: tools/formant_asan_main.cpp build/asan/librvcx_asan.so
 host-asan-formant: build/asan/formant_main
 	ASAN_OPTIONS=abort_on_error=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 build/asan/formant_main
 
+# the same for the host twin of stage 19 (the live formant shift)
+build/asan/formant_live_main: tools/formant_live_asan_main.cpp build/asan/librvcx_asan.so
+	$(CLANGXX) -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer \
+	    -shared-libasan -Iinclude $< -Lbuild/asan -lrvcx_asan -Wl,-rpath,'$$ORIGIN' \
+	    -Wl,-rpath,$(dir $(shell $(CLANGXX) -print-file-name=libclang_rt.asan-x86_64.so)) -o $@
+
+host-asan-formant-live: build/asan/formant_live_main
+	ASAN_OPTIONS=abort_on_error=1:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 build/asan/formant_live_main
+
 # ---- the same host pass under ThreadSanitizer (tools/host_tsan.sh runs tools/host_tickets_driver.py on it): conversion
 # tickets are the first code of the library where the state of two requests can meet
 TSAN_FLAGS := --cuda-host-only -O1 -g -std=c++17 -fPIC -Wno-pass-failed -Wno-unused-result -fsanitize=thread \
@@ -78,4 +87,4 @@ host-tsan: build/tsan/librvcx_tsan.so
 clean:
 	rm -rf build $(OUT)
 
-.PHONY: all clean host-asan host-tsan
+.PHONY: all clean host-asan host-asan-formant host-asan-formant-live host-tsan

@@ -1025,11 +1025,102 @@ int rvcx_fx_pitch_shift_formant_host(const float* x, int64_t n, int channels, in
                                      const rvcx_fx_formant_params*, float* y);
 int rvcx_fx_formant_envelope_host(const float* L, int N, int nc, int iterations, float* E);
 
+/* ---- live formant shift ---------------------------------------------------------------------------------------------------
+ * Stage 19 is stage 17 without a source, made causal on stage 16's grid, so that a live-stream session can run it inside a
+ * step, at either edge: on the 16 kHz mono block in front of the ring (behind stage 16 when the side has one), where it moves
+ * the formants of the microphone signal before HuBERT and the F0 model see it, and on what leaves, behind the output resampler
+ * and stage 16 and in front of the board.  Stage 17 cannot run there: its grid has a last frame, its transform at 16 kHz is
+ * 1024 points (64 ms), and cut into blocks it leaves a seam at every block edge.  The definition is this project's own; tested
+ * against float64 (tests/formant_live_reference.py).
+ *
+ * 19 live formant shift, one channel, defined on x[0 .. ): everything the stream has received since open or reset.  There is no
+ *    last frame.  sr: stage 16's rule (a multiple of 100 Hz in 3200 .. 192000).
+ *    Geometry: stage 16's, not stage 13's.  N = the smallest power of two with 48 N >= sr, never below 512; H = N / 4, nb = N / 2
+ *    + 1, w stage 13's formula at this N.  Frame t is complete once sample t H + N / 2 - 1 has arrived; x = 0 in front of
+ *    sample 0; n samples complete T(n) frames as in stage 16.
+ *    Per frame, stage 17's rules from its own text: D, A2, top, eps and L; the true envelope (iterations + 1 lifts, E in float32
+ *    after each) with nc = floor(quefrency_ms sr / 1000), 1 <= nc <= N / 8 at THIS N (refused otherwise; the default 1.5 ms fits
+ *    at every admitted rate, since N >= sr / 48 > 0.012 sr); Es = E (there is no source); the warp in double; the gain with its
+ *    clamp; the energy scale with stage 17's summation order; Y = fl(g s) D with the imaginary parts of bins 0 and N / 2
+ *    dropped; fr_t = w irfft(Y_t) (scaling 1 / N).
+ *    Synthesis and delay are stage 16's: y[i] = (sum_t fr_t[i + N / 2 - t H]) / (sum_t w^2[i + N / 2 - t H]) over all frames t >=
+ *    0 that cover i, each sum in ascending t; the numerator in float32 from zero, the divisor in double, the quotient formed in
+ *    double and rounded once.  Delay: d = N samples.  A step that has received the samples below (k + 1) Bn emits y[k Bn - N +
+ *    i], i < Bn, and 0 where that index is negative.
+ *    Off: amount == 0 or ratio == 1 keeps the stage in the path with its delay; it emits x[k Bn - N + i], the delayed input bit
+ *    for bit.  Frames and sums keep running (every gain is then 1), so switching it on in mid-session starts from correct
+ *    overlap-add sums, and the latency never changes.
+ *    Parameter changes: frame t uses the values in force in the step that completes it, and a step emits by the values in force
+ *    in it.
+ *    On the device the transforms (those of the lifts too), E and the numerator are float32.  The host twin transforms and
+ *    synthesises in double and rounds D, E (after every lift), W, g, s and y as stage 17's twin does.
+ *    The result depends on the samples received and the parameter history alone: the block length (shorter than H, so that a
+ *    step completes no frame, or longer than N), the other streams of a group and a repeated step change no bit.
+ *
+ * State, per stream and side: the last N samples and the N overlap-add sums behind the last sample emitted -- a frame has no
+ * recurrence across frames.  It is the session's own memory and exists twice, like stage 16's: a step reads set cur and writes
+ * the other one whole.  Nothing in it is a stored position.  Two launches per side and step: the frames the step completes side
+ * by side, one 256-lane workgroup each (skipped when the step completes none), then one workgroup per stream that adds them to
+ * the sums in ascending t, emits the block and writes the new state; no atomics, no host synchronisation.
+ *
+ * Errors: a value out of the ranges below or not finite, a rate that is not the side's (or 0) or out of range, channels other
+ * than 0 or 1, nc outside 1 .. N / 8 return -1 with a message and write or open nothing. */
+typedef struct {
+  int32_t sample_rate, channels; /* 0 or the rate of the side; 0 or 1 */
+  float ratio;                  /* 0.5 .. 2 (1): formants move up by this factor */
+  float amount;                 /* 0 .. 1 (1) */
+  float quefrency_ms;           /* > 0 with 1 <= nc <= N / 8 (1.5) */
+  int32_t iterations;           /* 0 .. 16 (8) */
+  float max_gain_db;            /* 0 .. 48 (24) */
+  int32_t keep_energy;          /* 0 or 1 (1) */
+} rvcx_live_formant_params;
+/* one side of a session: params == NULL, the side is absent */
+typedef struct {
+  const rvcx_live_formant_params* params;
+} rvcx_stream_fm_side;
+typedef struct {
+  rvcx_stream_fm_side in;       /* behind the input resampler and stage 16, in front of the ring, at 16 kHz */
+  rvcx_stream_fm_side out;      /* behind the output resampler and stage 16, in front of the board, mono, at the delivery rate */
+} rvcx_stream_fm;
+/* N of stage 19 at this rate: the delay a side adds, in samples of its rate; -1 for a refused rate (host only) */
+int rvcx_stream_formant_delay(int sr);
+/* T(n), N and nc at this rate and quefrency; nc outside 1 .. N / 8 is refused (host only) */
+int rvcx_stream_formant_frames(int64_t n, int sr, float quefrency_ms, int64_t* T, int32_t* N, int32_t* nc);
+/* fm == NULL or both sides absent: rvcx_stream_open_dn, launch for launch and bit for bit.  Every refusal of both sides is made
+ * first, and nothing is opened.  Order in the step: input resampler, stage 16 in, stage 19 in, ring; output resampler, stage 16
+ * out, stage 19 out, board.  The in16k tap of rvcx_stream_last_taps returns what entered the ring, behind both. */
+int rvcx_stream_open_fm(rvcx_ctx*, int model_id, const rvcx_stream_cfg*, const rvcx_stream_io*, const rvcx_fx_params* fx,
+                        const rvcx_stream_dn* dn, const rvcx_stream_fm* fm, const rvcx_params* p, const int32_t* sid,
+                        const float* pitch, int* stream_id);
+/* new values for side 0 (input) or 1 (output) from the next step on; every value may change (geometry and delay depend on the
+ * rate alone).  A refused value (a quefrency_ms outside the bound among them): -1, nothing changed.  Refused for a side that
+ * was absent at open. */
+int rvcx_stream_set_formant(rvcx_ctx*, int stream_id, int side, const rvcx_live_formant_params*);
+/* device ms of the two sides in the last step ({input, output}; 0 for an absent side).  In rvcx_last_timing the input side is
+ * counted in the "F0" interval, the output side in "SOLA + copies".  rvcx_stream_delays adds N of each present side. */
+int rvcx_stream_last_fm_ms(rvcx_ctx*, int stream_id, float* ms2);
+/* a side without a session and without a model: S mono rows of `frames` samples (x_hd: S x frames) at rate sr, cut into blocks
+ * of block_frames 10 ms frames (frames must be a multiple of block_frames * sr / 100), through the same state and kernel code
+ * a session runs per step; y_hd receives S x frames, delayed by N.  Optional taps for the T(frames) frames completed: E_hd and
+ * g_hd (S, T, nb), s_hd (S, T) */
+int rvcx_op_stream_formant(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int sr, int block_frames,
+                           const rvcx_live_formant_params*, float* y_hd, float* E_hd, float* g_hd, float* s_hd);
+/* an op-level entry for verification, like the other rvcx_op_*: the same with a parameter history, as rvcx_stream_set_formant
+ * writes one in a session, so that a session under set_formant can be held to the op bit for bit.  params[i] (n_params >= 1 of
+ * them) is in force from block from_block[i] on; from_block[0] == 0, ascending.  An application has no use for it */
+int rvcx_op_stream_formant_history(rvcx_ctx*, const float* x_hd, int S, int64_t frames, int sr, int block_frames, int n_params,
+                                   const rvcx_live_formant_params* params, const int64_t* from_block, float* y_hd, float* E_hd,
+                                   float* g_hd, float* s_hd);
+/* host only, no context: stage 19 on the whole signal x[0 .. n) -> y (n samples, delayed by N).  Optional taps for the T(n)
+ * frames: D (T, nb, 2) float32, E and g (T, nb), s (T) */
+int rvcx_fx_formant_live_host(const float* x, int64_t n, int sr, const rvcx_live_formant_params*, float* y, float* D, float* E,
+                              float* g, float* s);
+
 /* ---- instrumentation ------------------------------------------------------------------- */
 /* per-stage GPU milliseconds (HIP events on the library's stream) of the last
  * rvcx_convert_batch: {highpass, rmvpe, hubert, index, enc_p, flow, decoder, post, total}; of the last rvcx_stream_step:
  * {0, F0, HuBERT, blend + mix, enc_p, flow, decoder, SOLA + copies, total} -- a session's input resampler is counted in the
- * F0 interval, its output resampler in "SOLA + copies", and so are the input and the output side of stage 16; of the last
+ * F0 interval, its output resampler in "SOLA + copies", and so are the input and the output side of stages 16 and 19; of the last
  * rvcx_fx_chain: {high-pass, compressor, gate, reverb, low
  * shelf, high shelf, chorus, copies + layout, total} (summed over the call's groups); of the last rvcx_fx_loudness: {copies +
  * layout, chunk states, carry, K-weighting + energy, hop sums + gates, true peak, copies back, 0, total}; of the last

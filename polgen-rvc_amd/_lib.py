@@ -182,6 +182,8 @@ SYMBOLS = [
     "rvcx_stream_last_dn_ms", "rvcx_op_stream_denoise", "rvcx_fx_denoise_live_host",
     "rvcx_fx_formant_frames", "rvcx_fx_formant", "rvcx_fx_pitch_shift_formant", "rvcx_op_fx_formant_taps",
     "rvcx_fx_formant_host", "rvcx_fx_pitch_shift_formant_host", "rvcx_fx_formant_envelope_host",
+    "rvcx_stream_formant_delay", "rvcx_stream_formant_frames", "rvcx_stream_open_fm", "rvcx_stream_set_formant",
+    "rvcx_stream_last_fm_ms", "rvcx_op_stream_formant", "rvcx_op_stream_formant_history", "rvcx_fx_formant_live_host",
     "rvcx_op_groupnorm_gelu", "rvcx_op_hubert_conv0", "rvcx_op_sine_source", "rvcx_op_randn", "rvcx_op_reflect_pad",
     "rvcx_op_mel_post", "rvcx_op_decode_f0", "rvcx_op_avgpool2", "rvcx_op_gru_input", "rvcx_op_upsample_protect",
     "rvcx_kmeans", "rvcx_ivf_assign", "rvcx_kmeans_exhaustive", "rvcx_index_features",
@@ -326,6 +328,14 @@ def lib() -> C.CDLL:
         _lib.rvcx_fx_formant_host.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
         _lib.rvcx_fx_pitch_shift_formant_host.argtypes = [vp, i64, i, i, d, vp, vp]
         _lib.rvcx_fx_formant_envelope_host.argtypes = [vp, i, i, i, vp]
+        _lib.rvcx_stream_formant_delay.argtypes = [i]
+        _lib.rvcx_stream_formant_frames.argtypes = [i64, i, f, vp, vp, vp]
+        _lib.rvcx_stream_open_fm.argtypes = [vp, i, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_stream_set_formant.argtypes = [vp, i, i, vp]
+        _lib.rvcx_stream_last_fm_ms.argtypes = [vp, i, vp]
+        _lib.rvcx_op_stream_formant.argtypes = [vp, vp, i, i64, i, i, vp, vp, vp, vp, vp]
+        _lib.rvcx_op_stream_formant_history.argtypes = [vp, vp, i, i64, i, i, i, vp, vp, vp, vp, vp, vp]
+        _lib.rvcx_fx_formant_live_host.argtypes = [vp, i64, i, vp, vp, vp, vp, vp, vp]
     return _lib
 
 
@@ -874,6 +884,17 @@ def _live_denoise(params, sr=0):
     return LiveDenoiseParams.make(sr, **v), noise
 
 
+def _stream_denoise(sides):
+    """rvcx_stream_dn from the two sides, each None or what _live_denoise returned (which the caller keeps alive)"""
+    dn = StreamDenoise()
+    for name, sd in zip(("inp", "out"), sides):
+        if sd is not None:
+            p, z = sd
+            setattr(dn, name, StreamDenoiseSide(C.cast(C.pointer(p), C.c_void_p), None if z is None else z.ctypes.data,
+                                                0 if z is None else z.shape[0]))
+    return dn
+
+
 def stream_denoise_delay(sr: int) -> int:
     """N of stage 16 at this rate: the samples a side delays its signal by (RvcxError for a refused rate)"""
     N = int(lib().rvcx_stream_denoise_delay(int(sr)))
@@ -917,6 +938,95 @@ def fx_denoise_live_host(x, sr, params=None, noise=None, taps=False):
     _fx_host("fx_denoise_live_host", lib().rvcx_fx_denoise_live_host(
         x.ctypes.data, x.shape[0], int(sr), None if z is None else z.ctypes.data, 0 if z is None else z.shape[0], C.byref(p),
         y.ctypes.data, *[t[k].ctypes.data if k in t else None for k in ("D", "S", "f", "m")]))
+    return (y, t) if taps else y
+
+
+# ---- live formant shift on the host (rvcx.h stage 19) ------------------------------------------------------------------------------
+class LiveFormantParams(C.Structure):
+    """rvcx_live_formant_params; make() fills the defaults of include/rvcx.h stage 19 (semitones= sets ratio through
+    formant_ratio, the float32 rule of stage 17's layer)"""
+    _fields_ = [("sample_rate", C.c_int32), ("channels", C.c_int32), ("ratio", C.c_float), ("amount", C.c_float),
+                ("quefrency_ms", C.c_float), ("iterations", C.c_int32), ("max_gain_db", C.c_float), ("keep_energy", C.c_int32)]
+    DEFAULTS = dict(ratio=1.0, amount=1.0, quefrency_ms=1.5, iterations=8, max_gain_db=24.0, keep_energy=1)
+    INTS = ("iterations", "keep_energy")
+
+    @classmethod
+    def make(cls, sr=0, **values):
+        if "semitones" in values:
+            if "ratio" in values:
+                raise RvcxError("LiveFormantParams: ratio or semitones, not both")
+            values["ratio"] = formant_ratio(values.pop("semitones"))
+        unknown = set(values) - set(cls.DEFAULTS)
+        if unknown:
+            raise RvcxError(f"LiveFormantParams: unknown value(s) {sorted(unknown)}")
+        v = dict(cls.DEFAULTS, **values)
+        for k in cls.INTS:
+            if int(v[k]) != v[k]:
+                raise RvcxError(f"LiveFormantParams: {k} must be an integer")
+        return cls(int(sr), 1, *[(int if k in cls.INTS else float)(v[k]) for k in cls.DEFAULTS])
+
+    def values(self):
+        return {k: getattr(self, k) for k in self.DEFAULTS}
+
+
+class StreamFormantSide(C.Structure):
+    """rvcx_stream_fm_side: params NULL, the side is absent"""
+    _fields_ = [("params", C.c_void_p)]
+
+
+class StreamFormant(C.Structure):
+    """rvcx_stream_fm (`in` is `inp` here)"""
+    _fields_ = [("inp", StreamFormantSide), ("out", StreamFormantSide)]
+
+
+def _live_formant(params, sr=0):
+    """LiveFormantParams from a LiveFormantParams or a dict of values (semitones= in place of ratio=)"""
+    if isinstance(params, LiveFormantParams):
+        return LiveFormantParams(int(sr), 1, *[getattr(params, k) for k in LiveFormantParams.DEFAULTS])
+    return LiveFormantParams.make(sr, **dict(params or {}))
+
+
+def stream_formant_delay(sr: int) -> int:
+    """N of stage 19 at this rate: the samples a side delays its signal by (RvcxError for a refused rate)"""
+    N = int(lib().rvcx_stream_formant_delay(int(sr)))
+    if N < 0:
+        raise RvcxError("stream_formant_delay: the sample rate must be a multiple of 100 Hz within 3200 .. 192000")
+    return N
+
+
+def stream_formant_frames(n: int, sr: int, quefrency_ms=1.5):
+    """(T frames complete in n samples, N, nc) of stage 19"""
+    T, N, nc = C.c_int64(0), C.c_int32(0), C.c_int32(0)
+    _fx_host("stream_formant_frames", lib().rvcx_stream_formant_frames(int(n), int(sr), float(quefrency_ms), C.byref(T),
+                                                                       C.byref(N), C.byref(nc)))
+    return int(T.value), int(N.value), int(nc.value)
+
+
+def _live_formant_taps(S, n, sr, want, host):
+    if not want:
+        return {}
+    N = stream_formant_delay(sr)
+    T = stream_denoise_frames(n, sr)[0]
+    shape = (T, N // 2 + 1) if S is None else (S, T, N // 2 + 1)
+    t = dict(E=np.zeros(shape, np.float32), g=np.zeros(shape, np.float32), s=np.zeros(shape[:-1], np.float32))
+    if host:
+        t.update(D=np.zeros(shape + (2,), np.float32))
+    return t
+
+
+def fx_formant_live_host(x, sr, params=None, taps=False):
+    """stage 19 on the host (transforms and synthesis in double) on the whole signal -> y delayed by N, or (y, dict of the
+    taps D (T, nb, 2), E, g (T, nb) and s (T))"""
+    x = f32(x)
+    if x.ndim != 1:
+        raise RvcxError("fx_formant_live_host: one channel of shape (samples,) expected")
+    p = _live_formant(params, sr)
+    y = np.zeros_like(x)
+    rate_ok = lib().rvcx_stream_formant_delay(int(sr)) > 0          # (a refused rate: the library says so below)
+    t = _live_formant_taps(None, x.shape[0], sr, taps, True) if rate_ok else {}
+    _fx_host("fx_formant_live_host", lib().rvcx_fx_formant_live_host(
+        x.ctypes.data, x.shape[0], int(sr), C.byref(p), y.ctypes.data,
+        *[t[k].ctypes.data if k in t else None for k in ("D", "E", "g", "s")]))
     return (y, t) if taps else y
 
 
@@ -1100,6 +1210,7 @@ class StreamSession:
         self.out_channels = int(lib().rvcx_stream_out_channels(ctx._h, sid))   # 2 when the effects board is on
         self.effects = None                                               # the eighteen values in force (a dict), or None
         self.denoise = [None, None]                                       # per side (in, out): the values in force, or None
+        self.formant = [None, None]                                       # the same for the live formant shift
         self.noise_len = int(lib().rvcx_stream_noise_len(ctx._h, sid))
         self.frames = int(lib().rvcx_stream_frames(ctx._h, sid))          # T of the TextEncoder
         din, dout = C.c_int32(0), C.c_int32(0)
@@ -1206,6 +1317,29 @@ class StreamSession:
         """device ms of the input and the output noise gate in the last step (rvcx_stream_last_dn_ms; 0 for an absent side)"""
         ms = (C.c_float * 2)()
         self._ctx._ck(lib().rvcx_stream_last_dn_ms(self._ctx._h, self.id, ms), "stream_last_dn_ms")
+        return float(ms[0]), float(ms[1])
+
+    def set_formant(self, side, **changes):
+        """rvcx_stream_set_formant: new values for some of the six LiveFormantParams names (semitones= in place of ratio=) on
+        side "in" or "out", applied from the next step on; the others keep their current value.  All state is kept.  A refused
+        value changes nothing; a side that was absent at open refuses the call."""
+        if side not in self.SIDES:
+            raise RvcxError("StreamSession.set_formant: side must be 'in' or 'out'")
+        k = self.SIDES[side]
+        if self.formant[k] is None:
+            raise RvcxError("StreamSession.set_formant: the session was opened without a formant shift on this side (its "
+                            "delay is fixed at open)")
+        base = dict(self.formant[k])
+        if "semitones" in changes:
+            base.pop("ratio")
+        p = LiveFormantParams.make(0, **dict(base, **changes))
+        self._ctx._ck(lib().rvcx_stream_set_formant(self._ctx._h, self.id, k, C.byref(p)), "stream_set_formant")
+        self.formant[k] = p.values()
+
+    def last_fm_ms(self):
+        """device ms of the input and the output formant shift in the last step (rvcx_stream_last_fm_ms; 0 for an absent side)"""
+        ms = (C.c_float * 2)()
+        self._ctx._ck(lib().rvcx_stream_last_fm_ms(self._ctx._h, self.id, ms), "stream_last_fm_ms")
         return float(ms[0]), float(ms[1])
 
     def reset(self):
@@ -1615,15 +1749,17 @@ class Context:
 
     def stream_open(self, model_id, params: "Params", sids, pitches, block_frames, context_frames, crossfade_frames,
                     search_frames, in_rate=0, in_channels=1, out_rate=0, effects=None, denoise_in=None,
-                    denoise_out=None) -> "StreamSession":
+                    denoise_out=None, formant_in=None, formant_out=None) -> "StreamSession":
         """rvcx_stream_open_io: len(sids) lock-step live streams on voice model `model_id` (frames of 10 ms).  in_rate /
         in_channels: what step() takes (0 or 16000 with one channel: 16 kHz mono); out_rate: what it returns (0 or the
         model's rate: the model's rate).  effects: a dict of add_effects names laid over FX_UI_DEFAULTS, or an FxParams --
         the board runs inside every step on what would have left and step() returns stereo (rvcx_stream_open_fx).
         denoise_in / denoise_out: a dict of LiveDenoiseParams values (with noise= a clip for mode 0), or a LiveDenoiseParams --
         live noise reduction on the 16 kHz block in front of the ring / on what leaves, in front of the board; each side
-        delays its signal by stream_denoise_delay(rate) samples (rvcx_stream_open_dn).  With the defaults this is
-        rvcx_stream_open."""
+        delays its signal by stream_denoise_delay(rate) samples (rvcx_stream_open_dn).
+        formant_in / formant_out: a dict of LiveFormantParams values (semitones= in place of ratio=), or a LiveFormantParams --
+        the live formant shift behind the noise gate of that side; each side delays its signal by stream_formant_delay(rate)
+        samples (rvcx_stream_open_fm).  With the defaults this is rvcx_stream_open."""
         values = None if effects is None else fx_values(effects)
         sid, pit = i32(np.atleast_1d(sids)), f32(np.atleast_1d(pitches))
         if sid.ndim != 1 or sid.shape != pit.shape or sid.shape[0] < 1:
@@ -1631,22 +1767,27 @@ class Context:
         cfg = StreamCfg(int(sid.shape[0]), int(block_frames), int(context_frames), int(crossfade_frames), int(search_frames))
         io = StreamIO(int(in_rate), int(in_channels), int(out_rate), 0)
         h = C.c_int(0)
-        if denoise_in is not None or denoise_out is not None:
-            # stage 16 on the 16 kHz block in front of the ring and / or on what leaves, in front of the board
-            sides = [None if v is None else _live_denoise(v) for v in (denoise_in, denoise_out)]
-            dn = StreamDenoise()
-            for name, sd in zip(("inp", "out"), sides):
-                if sd is not None:
-                    p, z = sd
-                    setattr(dn, name, StreamDenoiseSide(C.cast(C.pointer(p), C.c_void_p), None if z is None else z.ctypes.data,
-                                                        0 if z is None else z.shape[0]))
+        if any(v is not None for v in (denoise_in, denoise_out, formant_in, formant_out)):
+            # stage 16 on the 16 kHz block in front of the ring and / or on what leaves, in front of the board; stage 19 behind
+            # it on either side.  Without a formant side the session is opened as it was before stage 19 existed
+            dsides = [None if v is None else _live_denoise(v) for v in (denoise_in, denoise_out)]
+            fsides = [None if v is None else _live_formant(v) for v in (formant_in, formant_out)]
+            dn, fm = _stream_denoise(dsides), StreamFormant()
+            for name, fs in zip(("inp", "out"), fsides):
+                if fs is not None:
+                    setattr(fm, name, StreamFormantSide(C.cast(C.pointer(fs), C.c_void_p)))
             fx = None if values is None else FxParams.make(values, 0, 0)
-            self._ck(lib().rvcx_stream_open_dn(self._h, int(model_id), C.byref(cfg), C.byref(io),
-                                               None if fx is None else C.byref(fx), C.byref(dn), C.byref(params),
-                                               sid.ctypes.data, pit.ctypes.data, C.byref(h)), "stream_open")
+            front = (self._h, int(model_id), C.byref(cfg), C.byref(io), None if fx is None else C.byref(fx))
+            back = (C.byref(params), sid.ctypes.data, pit.ctypes.data, C.byref(h))
+            if fsides == [None, None]:
+                self._ck(lib().rvcx_stream_open_dn(*front, C.byref(dn), *back), "stream_open")
+            else:
+                self._ck(lib().rvcx_stream_open_fm(*front, None if dsides == [None, None] else C.byref(dn), C.byref(fm), *back),
+                         "stream_open")
             se = StreamSession(self, int(h.value), cfg, io, self.synth_upp(model_id))
             se.effects = values
-            se.denoise = [None if sd is None else sd[0].values() for sd in sides]
+            se.denoise = [None if sd is None else sd[0].values() for sd in dsides]
+            se.formant = [None if fs is None else fs.values() for fs in fsides]
             return se
         if values is None:
             self._ck(lib().rvcx_stream_open_io(self._h, int(model_id), C.byref(cfg), C.byref(io), C.byref(params),
@@ -1702,6 +1843,28 @@ class Context:
                                               zp, C.c_int64(zn), y.ctypes.data,
                                               *[t[k].ctypes.data if k in t else None for k in ("S", "f", "m")]),
                  "op_stream_denoise")
+        return (y, t) if taps else y
+
+    def stream_formant(self, x, sr: int, block_frames: int, params=None, taps=False, history=None):
+        """rvcx_op_stream_formant: a session's formant shift without a session.  x (S, frames) float32 at rate sr, cut into blocks
+        of block_frames * sr / 100 samples and sent through the state and kernels a session runs per step -> (S, frames),
+        delayed by stream_formant_delay(sr).  params: a dict of LiveFormantParams values or a LiveFormantParams.  history: further
+        (block, params) pairs in ascending block order -- what set_formant in front of step `block` leaves in a session.
+        taps=True: (y, dict of E, g (S, T, nb) and s (S, T))."""
+        x = f32(x)
+        if x.ndim != 2:
+            raise RvcxError("stream_formant: x must be (S, frames)")
+        S, frames = x.shape
+        plist = [_live_formant(params, sr)] + [_live_formant(q, sr) for _, q in (history or [])]
+        arr = (LiveFormantParams * len(plist))(*plist)
+        at = np.asarray([0] + [int(k) for k, _ in (history or [])], np.int64)
+        y = np.full((S, frames), np.nan, np.float32)
+        rate_ok = lib().rvcx_stream_formant_delay(int(sr)) > 0      # (a refused rate: the library says so below)
+        t = _live_formant_taps(S, frames, sr, taps, False) if rate_ok else {}
+        self._ck(lib().rvcx_op_stream_formant_history(self._h, x.ctypes.data, S, C.c_int64(frames), int(sr), int(block_frames),
+                                                      len(plist), arr, at.ctypes.data, y.ctypes.data,
+                                                      *[t[k].ctypes.data if k in t else None for k in ("E", "g", "s")]),
+                 "op_stream_formant")
         return (y, t) if taps else y
 
     def load_rmvpe(self, cfg_struct, state: dict):

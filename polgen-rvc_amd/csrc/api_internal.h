@@ -12,6 +12,7 @@
 #include "ctx.h"
 #include "denoise_live.h"
 #include "effects.h"
+#include "formant_live.h"
 #include "layers.h"
 #include "models.h"
 #include "ops.h"
@@ -128,7 +129,26 @@ struct StreamSession {
     hipEvent_t ev[2] = {nullptr, nullptr};
   } dn[2];
   float dn_ms[2] = {0, 0};                 // rvcx_stream_last_dn_ms
+  // live formant shift (rvcx_stream_open_fm; rvcx.h stage 19): side 0 behind the input noise gate in front of the ring, side 1
+  // behind the output noise gate in front of the board.  State sets as above; tables, scratch and staging are the session's own
+  struct FmSide {
+    std::unique_ptr<FmLive> d;             // null: the side is absent
+    rvcx_live_formant_params p{};          // the parameters in force
+    float* tables = nullptr;               // w (N floats), then the twiddles (N / 2 pairs)
+    float* stage = nullptr;                // (S, B): side 0, the block in front of the stage; side 1, what the side emits
+    hipEvent_t ev[2] = {nullptr, nullptr};
+  } fm[2];
+  float fm_ms[2] = {0, 0};                 // rvcx_stream_last_fm_ms
   ~StreamSession() {
+    for (FmSide& sd : fm) {
+      if (sd.d)
+        for (void* q : {(void*)sd.d->state[0], (void*)sd.d->state[1], (void*)sd.d->fr})
+          if (q) (void)hipFree(q);
+      for (void* q : {(void*)sd.tables, (void*)sd.stage})
+        if (q) (void)hipFree(q);
+      for (hipEvent_t e : sd.ev)
+        if (e) (void)hipEventDestroy(e);
+    }
     for (DnSide& sd : dn) {
       if (sd.d)
         for (void* q : {(void*)sd.d->state[0], (void*)sd.d->state[1], (void*)sd.d->acc})

@@ -204,7 +204,10 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
     float* blocks = se.blocks[se.cur ^ 1];
     StreamSession::DnSide& dn_in = se.dn[0];
     StreamSession::DnSide& dn_out = se.dn[1];
-    float* raw = dn_in.d ? dn_in.stage : blocks;      // a session with an input noise gate: the 16 kHz block as it came
+    StreamSession::FmSide& fm_in = se.fm[0];
+    StreamSession::FmSide& fm_out = se.fm[1];
+    // a session with an input noise gate or formant shift: the 16 kHz block as it came goes to the first of them
+    float* raw = dn_in.d ? dn_in.stage : (fm_in.d ? fm_in.stage : blocks);
     if (se.in.on) {
       const size_t row = (size_t)se.in.g.B_in * se.in.g.channels;
       for (int s = 0; s < S; ++s)
@@ -217,8 +220,13 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
     }
     if (dn_in.d) {                                    // stage 16 in front of the ring, from the state it carries
       RVCX_HIP(hipEventRecord(dn_in.ev[0], st));
-      dn_live_step(*dn_in.d, raw, blk, se.cur, se.step, blocks, blk, st);
+      dn_live_step(*dn_in.d, raw, blk, se.cur, se.step, fm_in.d ? fm_in.stage : blocks, blk, st);
       RVCX_HIP(hipEventRecord(dn_in.ev[1], st));
+    }
+    if (fm_in.d) {                                    // stage 19 behind it, in front of the ring
+      RVCX_HIP(hipEventRecord(fm_in.ev[0], st));
+      fm_live_step(*fm_in.d, fm_in.stage, blk, se.cur, se.step, blocks, blk, st);
+      RVCX_HIP(hipEventRecord(fm_in.ev[1], st));
     }
     const float* ring_old = se.ring[se.cur];
     float* ring = se.ring[se.cur ^ 1];
@@ -292,6 +300,13 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
       RVCX_HIP(hipEventRecord(dn_out.ev[1], st));
       dres = dn_out.stage;
     }
+    // (6c) a session with an output formant shift: stage 19 behind the gate, in front of the board
+    if (fm_out.d) {
+      RVCX_HIP(hipEventRecord(fm_out.ev[0], st));
+      fm_live_step(*fm_out.d, dres, Lo, se.cur, se.step, fm_out.stage, Lo, st);
+      RVCX_HIP(hipEventRecord(fm_out.ev[1], st));
+      dres = fm_out.stage;
+    }
     // (7) a session with effects: the board on what would have left, from the state it carries; stereo leaves
     if (se.fx) {
       fx_live_step(*se.fx, dres, Lo, 1, se.cur, se.step, se.fx_out, 2 * Lo, st, ev + 8);
@@ -317,6 +332,8 @@ int rvcx_stream_step(rvcx_ctx* ctx, int stream_id, const float* const* block16k,
       }
       for (int k = 0; k < 2; ++k)
         if (se.dn[k].d) RVCX_HIP(hipEventElapsedTime(&se.dn_ms[k], se.dn[k].ev[0], se.dn[k].ev[1]));
+      for (int k = 0; k < 2; ++k)
+        if (se.fm[k].d) RVCX_HIP(hipEventElapsedTime(&se.fm_ms[k], se.fm[k].ev[0], se.fm[k].ev[1]));
     }
     A.reset();
     done = &se;
@@ -342,6 +359,9 @@ int rvcx_stream_reset(rvcx_ctx* ctx, int stream_id) {
   for (StreamSession::DnSide& sd : se.dn)
     if (sd.d)
       for (float* q : sd.d->state) RVCX_HIP(hipMemsetAsync(q, 0, (size_t)se.S * sd.d->per_stream * 4, C->stream));
+  for (StreamSession::FmSide& sd : se.fm)
+    if (sd.d)
+      for (float* q : sd.d->state) RVCX_HIP(hipMemsetAsync(q, 0, (size_t)se.S * fm_live_per_stream(*sd.d) * 4, C->stream));
   RVCX_HIP(hipStreamSynchronize(C->stream));
   se.step = 0;
   API_END
@@ -378,8 +398,10 @@ int rvcx_stream_delays(rvcx_ctx* ctx, int stream_id, int32_t* in_delay_16k, int3
   auto it = ctx->sessions.find(stream_id);
   if (it == ctx->sessions.end()) return -1;
   const StreamSession& se = *it->second;
-  if (in_delay_16k) *in_delay_16k = (se.in.on ? se.in.g.delay : 0) + (se.dn[0].d ? se.dn[0].d->g.N : 0);
-  if (out_delay) *out_delay = (se.out.on ? se.out.g.delay : 0) + (se.dn[1].d ? se.dn[1].d->g.N : 0);
+  if (in_delay_16k)
+    *in_delay_16k = (se.in.on ? se.in.g.delay : 0) + (se.dn[0].d ? se.dn[0].d->g.N : 0) + (se.fm[0].d ? se.fm[0].d->g.N : 0);
+  if (out_delay)
+    *out_delay = (se.out.on ? se.out.g.delay : 0) + (se.dn[1].d ? se.dn[1].d->g.N : 0) + (se.fm[1].d ? se.fm[1].d->g.N : 0);
   return 0;
 }
 

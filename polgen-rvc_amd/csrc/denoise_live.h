@@ -35,6 +35,18 @@ inline double dn_live_nt(double ms, int sr, int H) { return std::floor(ms * (dou
 inline double dn_live_c(int H, int sr, double tc) { return std::exp(-(double)H / ((double)sr * tc)); }
 // frames complete once n samples have arrived: frame t needs the samples below t H + N / 2
 inline long dn_live_frames(long n, int N, int H) { return n >= N / 2 ? (n - N / 2) / H + 1 : 0; }
+// sum of w^2 over the frames t >= 0 that cover sample j >= 0, in ascending t (the live formant stage divides by it too)
+__host__ __device__ inline double dn_live_den(const float* w, long j, int N, int H) {
+#pragma clang fp contract(off)           // every product rounded, whatever the including file has set
+  const long a = (j - N / 2 + H) / H, tlo = a > 0 ? a : 0, thi = (j + N / 2) / H;
+  double den = 0.0;
+  for (long t = tlo; t <= thi; ++t) {
+    const long i = j + N / 2 - t * H;
+    if (i < 0 || i >= N) continue;                     // (never: the bounds of tlo and thi)
+    den += (double)w[i] * (double)w[i];
+  }
+  return den;
+}
 
 struct DnLiveValues {                    // rvcx_live_denoise_params without the signal's shape and the widths
   int mode;

@@ -60,18 +60,6 @@ __host__ __device__ inline int dn_live_wt(long t, int nt) {
   return s;
 }
 
-// sum of w^2 over the frames t >= 0 that cover sample j >= 0, in ascending t
-__host__ __device__ inline double dn_live_den(const float* w, long j, int N, int H) {
-  const long a = (j - N / 2 + H) / H, tlo = a > 0 ? a : 0, thi = (j + N / 2) / H;
-  double den = 0.0;
-  for (long t = tlo; t <= thi; ++t) {
-    const long i = j + N / 2 - t * H;
-    if (i < 0 || i >= N) continue;                     // (never: the bounds of tlo and thi)
-    den += (double)w[i] * (double)w[i];
-  }
-  return den;
-}
-
 __global__ __launch_bounds__(256) void dn_live_kernel(const DnLiveArgs q) {
   extern __shared__ float2 a[];                        // N pairs, then A2 of the frame (nb floats)
   const int N = q.N, H = q.H, nb = q.nb, logN = q.logN, nf = q.nf, nt = q.nt, tid = threadIdx.x;

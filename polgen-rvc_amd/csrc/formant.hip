@@ -2,16 +2,10 @@
 // linear warp, a clamp), so no decision can fall the other way between float32 and float64.
 //
 // Kernels (256 lanes; one row = one channel of one item):
-//   formant_frame_kernel   one workgroup per frame, everything in LDS and registers: window, stage 13's transform, A2 with the
-//                          frame's maximum, L, the iterations + 1 lifts, warp, gain, the two energy sums, Y = (g s) D, the inverse
-//                          transform and the window.  It writes the N windowed samples of the frame (and the taps when asked).
+//   formant_frame_kernel   one workgroup per frame, everything in LDS and registers (formant_device.h: fm_frame_body, shared with
+//                          the live stage).  It writes the N windowed samples of the frame (and the taps when asked).
 //   formant_ola_kernel     one lane per output sample (fft_device.h: ola_gather)
-// LDS: the N float pairs of the transform, nothing else (64 KiB at N = 8192).  A lane keeps its bins k = lane + 256 j of D, L and
-// E in registers.  The log spectra of the frame and of its source frame are both real and even, and so are their cepstra: they
-// travel as the real and the imaginary part of ONE complex sequence through every lift, so a source costs one more transform
-// per frame (its analysis), not 2 (iterations + 1) + 1, and when the last lift ends a[k] = (E[k], Es[k]) is what the warp gathers
-// from.  The
-// scratch of the two reductions lies in the same buffer, between barriers, while it holds nothing.
+// LDS: the N float pairs of the transform, nothing else (64 KiB at N = 8192).
 // Every index is bounded by the row's own T = len[r] / H + 1; nothing of a row is read or written beyond its frame T - 1.
 #include <algorithm>
 #include <cmath>
@@ -26,6 +20,7 @@
 #pragma clang fp contract(off)
 
 #include "fft_device.h"
+#include "formant_device.h"
 
 namespace rvcx {
 
@@ -33,171 +28,40 @@ namespace {
 
 constexpr double kPi = 3.14159265358979323846;
 
-__device__ __forceinline__ unsigned brev_n(int i, int logN) { return __brev((unsigned)i) >> (32 - logN); }
-
-// the largest value of a workgroup; scratch: 4 floats of LDS that hold nothing (barriers on both sides)
-__device__ __forceinline__ float block_max(float v, float* scratch) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
-  __syncthreads();
-  const float m = fmaxf(fmaxf(scratch[0], scratch[1]), fmaxf(scratch[2], scratch[3]));
-  __syncthreads();
-  return m;
-}
-
-// window and transform of the frame t of one signal: a[k] = D[k] in natural order
-__device__ __forceinline__ void frame_forward(float2* a, const float* __restrict__ x, long n, long t, const FxStretchGeom& g,
-                                              const float* __restrict__ w, const float2* __restrict__ tw) {
-  for (int i = threadIdx.x; i < g.N; i += 256) {
-    const long src = t * g.H - g.N / 2 + i;
-    const float v = (src >= 0 && src < n) ? w[i] * x[src] : 0.f;
-    a[brev_n(i, g.logN)] = make_float2(v, 0.f);
-  }
-  fft_lds(a, tw, g.N, g.logN);
-}
-
 __global__ __launch_bounds__(256) void formant_frame_kernel(const FxFormantDev d) {
   extern __shared__ float2 a[];
   const FxStretchGeom g = d.g;
-  const int r = blockIdx.y, N = g.N, nb = g.nb, logN = g.logN, tid = threadIdx.x;
+  const int r = blockIdx.y, nb = g.nb;
   const long t = blockIdx.x, n = d.len[r];
   if (t >= n / g.H + 1) return;
   const bool with_src = d.src != nullptr && d.has_src[r] != 0;
-  const bool tap = r == 0;
   const size_t tbase = (size_t)t * nb;
-  float* scratch = reinterpret_cast<float*>(a);
-
-  float dre[kFormantKpt], dim[kFormantKpt], L[kFormantKpt], Ls[kFormantKpt], E[kFormantKpt];
-  // ---- the item's frame: D, A2, L
-  frame_forward(a, d.x + (size_t)r * d.ld, n, t, g, d.w, d.tw);
-  float top = 0.f;
-#pragma unroll
-  for (int j = 0; j < kFormantKpt; ++j) {
-    const int k = tid + 256 * j;
-    const float2 z = k < nb ? a[k] : make_float2(0.f, 0.f);
-    dre[j] = z.x, dim[j] = z.y;
-    top = fmaxf(top, fm_a2(z.x, z.y));
-    if (tap && d.taps.D && k < nb) d.taps.D[tbase + k] = z;
+  FmFrameTaps taps;
+  if (r == 0) {
+    if (d.taps.D) taps.D = d.taps.D + tbase;
+    if (d.taps.E) taps.E = d.taps.E + tbase;
+    if (d.taps.Es) taps.Es = d.taps.Es + tbase;
+    if (d.taps.g) taps.g = d.taps.g + tbase;
+    if (d.taps.s) taps.s = d.taps.s + t;
   }
-  top = block_max(top, scratch);
-  {
-    const float eps = fm_eps(top);
-#pragma unroll
-    for (int j = 0; j < kFormantKpt; ++j) L[j] = fm_log(fm_a2(dre[j], dim[j]), eps), Ls[j] = 0.f;
-  }
-  // ---- the source's frame: Ls
-  if (with_src) {
-    frame_forward(a, d.src + (size_t)r * d.ld, n, t, g, d.w, d.tw);
-    float a2s[kFormantKpt];
-    float tops = 0.f;
-#pragma unroll
-    for (int j = 0; j < kFormantKpt; ++j) {
-      const int k = tid + 256 * j;
-      const float2 z = k < nb ? a[k] : make_float2(0.f, 0.f);
-      a2s[j] = fm_a2(z.x, z.y);
-      tops = fmaxf(tops, a2s[j]);
-    }
-    tops = block_max(tops, scratch);
-    const float eps = fm_eps(tops);
-#pragma unroll
-    for (int j = 0; j < kFormantKpt; ++j) Ls[j] = fm_log(a2s[j], eps);
-  }
-  // ---- the true envelope: V_0 = L, E = lift(V_i), V_{i+1} = max(L, E); the source rides in the imaginary part
-  {
-    float V[kFormantKpt], Vs[kFormantKpt];
-#pragma unroll
-    for (int j = 0; j < kFormantKpt; ++j) V[j] = L[j], Vs[j] = Ls[j];
-    const float inv = 1.f / (float)N;
-    const int nc = d.nc;
-    for (int it = 0; it <= d.v.iterations; ++it) {
-      // (the barrier that ended the last transform, or block_max, lies between the last reads of a and these writes)
-#pragma unroll
-      for (int j = 0; j < kFormantKpt; ++j) {
-        const int k = tid + 256 * j;
-        if (k < nb) {
-          const float2 z = make_float2(V[j], Vs[j]);
-          a[brev_n(k, logN)] = z;
-          if (k != 0 && k != N / 2) a[brev_n(N - k, logN)] = z;
-        }
-      }
-      fft_lds(a, d.tw, N, logN);                        // N c[q]: the inverse of a real even sequence is its forward over N
-      float2 c[kFormantCpt];
-#pragma unroll
-      for (int i = 0; i < kFormantCpt; ++i) {
-        const int q = tid + 256 * i;
-        const float2 z = q <= nc ? a[q] : make_float2(0.f, 0.f);
-        c[i] = make_float2(z.x * inv, z.y * inv);
-      }
-      __syncthreads();
-      for (int i = tid; i < N; i += 256) a[i] = make_float2(0.f, 0.f);
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < kFormantCpt; ++i) {
-        const int q = tid + 256 * i;
-        if (q <= nc) {                                  // c[N - q] = c[q]: the lifted cepstrum is even by construction
-          a[brev_n(q, logN)] = c[i];
-          if (q != 0) a[brev_n(N - q, logN)] = c[i];
-        }
-      }
-      fft_lds(a, d.tw, N, logN);
-#pragma unroll
-      for (int j = 0; j < kFormantKpt; ++j) {
-        const int k = tid + 256 * j;
-        const float2 e = k < nb ? a[k] : make_float2(0.f, 0.f);
-        E[j] = e.x;
-        V[j] = fmaxf(L[j], e.x), Vs[j] = fmaxf(Ls[j], e.y);
-      }
-      if (it < d.v.iterations) __syncthreads();
-    }
-  }
-  // ---- warp, gain and the energy sums; a[i] = (E[i], Es[i]) stays untouched until every lane has gathered
-  float gn[kFormantKpt];
-  double e0 = 0.0, e1 = 0.0;
-#pragma unroll
-  for (int j = 0; j < kFormantKpt; ++j) {
-    const int k = tid + 256 * j;
-    gn[j] = 1.f;
-    if (k < nb) {
-      const float W = with_src ? fm_warp([&](int i) { return a[i].y; }, k, nb, (double)d.v.ratio)
-                               : fm_warp([&](int i) { return a[i].x; }, k, nb, (double)d.v.ratio);
-      gn[j] = fm_gain(W, E[j], d.v.amount, d.limit);
-      fm_energy(fm_a2(dre[j], dim[j]), gn[j], k == 0 || k == nb - 1, e0, e1);
-      if (tap) {
-        if (d.taps.E) d.taps.E[tbase + k] = E[j];
-        if (d.taps.Es) d.taps.Es[tbase + k] = with_src ? a[k].y : a[k].x;
-        if (d.taps.g) d.taps.g[tbase + k] = gn[j];
-      }
-    }
-  }
-  float sc = 1.f;
-  __syncthreads();
-  if (d.v.keep_energy) {      // partial p over the bins k = p mod 256 in ascending k, then the partials in ascending p
-    double* part = reinterpret_cast<double*>(a);          // 512 doubles = 4 KiB <= 8 N bytes (N >= 512)
-    part[tid] = e0, part[256 + tid] = e1;
-    __syncthreads();
-    double s0 = 0.0, s1 = 0.0;
-    for (int p = 0; p < 256; ++p) s0 += part[p], s1 += part[256 + p];
-    sc = fm_scale(s0, s1);
-    __syncthreads();
-  }
-  if (tap && d.taps.s && tid == 0) d.taps.s[t] = sc;
-  // ---- Y = (g s) D, x = Re(F(conj Y)) / N with the forward transform F (conj Y at k, Y at N - k), the window
-#pragma unroll
-  for (int j = 0; j < kFormantKpt; ++j) {
-    const int k = tid + 256 * j;
-    if (k < nb) {
-      const float gs = gn[j] * sc;
-      const bool edge = k == 0 || k == N / 2;
-      const float re = gs * dre[j], im = edge ? 0.f : gs * dim[j];
-      a[brev_n(k, logN)] = make_float2(re, -im);
-      if (!edge) a[brev_n(N - k, logN)] = make_float2(re, im);
-    }
-  }
-  fft_lds(a, d.tw, N, logN);
-  float* out = d.fr + ((size_t)r * d.Tf + t) * N;
-  const float inv = 1.f / (float)N;
-  for (int i = tid; i < N; i += 256) out[i] = (a[i].x * inv) * d.w[i];
+  const FmFrameArgs q{g, d.v, d.nc, d.limit, d.w, d.tw};
+  const long j0 = t * g.H - g.N / 2;
+  const float* __restrict__ x = d.x + (size_t)r * d.ld;
+  const float* __restrict__ xs = d.src ? d.src + (size_t)r * d.ld : nullptr;
+  // sample i of frame t of a row: nothing in front of sample 0 or behind the row's last one
+  auto own = [&](int i, float& v) {
+    const long src = j0 + i;
+    if (src < 0 || src >= n) return false;
+    v = x[src];
+    return true;
+  };
+  auto other = [&](int i, float& v) {
+    const long src = j0 + i;
+    if (src < 0 || src >= n) return false;
+    v = xs[src];
+    return true;
+  };
+  fm_frame_body<kFormantKpt, kFormantCpt, true>(a, q, own, other, with_src, taps, d.fr + ((size_t)r * d.Tf + t) * g.N);
 }
 
 __global__ __launch_bounds__(256) void formant_ola_kernel(const FxFormantDev d, float* __restrict__ y, long ld_y) {

@@ -371,7 +371,8 @@ class VC:
 
     def stream_open(self, model, net_g, sids, pitches, f0_method, file_index, index_rate, version, protect, *,
                     block_ms, context_ms, crossfade_ms, search_ms, f0_min=50, f0_max=1100, input_sr=16000,
-                    input_channels=1, output_sr=None, effects=None, denoise_in=None, denoise_out=None):
+                    input_channels=1, output_sr=None, effects=None, denoise_in=None, denoise_out=None, formant_in=None,
+                    formant_out=None):
         """A live-stream session: len(sids) lock-step streams of one geometry on voice model ``net_g``.  Every
         ``session.step(blocks)`` takes one (S, block_ms * 16) float32 block of 16 kHz mono audio per stream and returns the
         converted (S, block_ms * tgt_sr / 1000) float32 blocks: rolling context, tail-only synthesis (Synthesizer.infer's
@@ -385,6 +386,9 @@ class VC:
         ``denoise_in`` / ``denoise_out``: a dict of ``LiveDenoiseParams`` values (``noise=`` a clip for the profile mode) -- the
         causal noise gate on the 16 kHz block in front of the model / on what leaves, in front of the board; each side adds
         ``stream_denoise_delay(rate)`` samples to the session's delay; ``session.set_denoise(side, **changes)`` changes values.
+        ``formant_in`` / ``formant_out``: a dict of ``LiveFormantParams`` values (``semitones=`` in place of ``ratio=``) -- the
+        causal formant shift behind that side's noise gate: on the microphone signal before HuBERT and the F0 model see it / on
+        what leaves; each side adds ``stream_formant_delay(rate)`` samples; ``session.set_formant(side, **changes)``.
         Checks of version, method and index as in ``pipeline_batch``."""
         if effects is not None:
             try:
@@ -415,7 +419,8 @@ class VC:
                          f0_method=f0_method)
         return ctx.stream_open(net_g.model_id, p, sids, pitches, Fb, Fc, Fx, Fs, in_rate=int(input_sr),
                                in_channels=int(input_channels), out_rate=0 if output_sr is None else int(output_sr),
-                               effects=effects, denoise_in=denoise_in, denoise_out=denoise_out)
+                               effects=effects, denoise_in=denoise_in, denoise_out=denoise_out, formant_in=formant_in,
+                               formant_out=formant_out)
 
     def pipeline_async(self, model, net_g, sid, audio, input_audio_path, pitch, f0_method, file_index, index_rate,
                        pitch_guidance, filter_radius, tgt_sr, resample_sr, volume_envelope, version, protect,

@@ -19,12 +19,18 @@ without each side, and the sides' own device times (rvcx_stream_last_dn_ms).  Th
 session without noise reduction always was, so it is the comparison.  Write that run to profiles/bench_stream_denoise.json
 (`--out`).
 
+With `--formant` every S is measured three more times with the live formant shift (rvcx_stream_open_fm, stage 19 at its
+defaults, +4 semitones) on the input side, on the output side and on both, next to the plain session of the same run: step time
+with and without each side, and the sides' own device times (rvcx_stream_last_fm_ms).  No bar is set on these times.  Write that
+run to profiles/bench_stream_formant.json (`--out`).
+
 The one criterion that can be derived is real time itself: a step must take less than the block it converts.  The result
 records, per S, whether the median and the p99 do, and the largest S whose p99 does.  Not part of bench.py.
 
     python tools/bench_stream.py [--streams 1,4,16,32] [--steps 200] [--warmup 20] [--repeats 3] [--model 48k|40k]
                                  [--in-rate 48000 --in-channels 2 --out-rate 48000] [--out profiles/bench_stream.json]
-    python tools/bench_stream.py --denoise --ab-steps 0 --out profiles/bench_stream_denoise.json"""
+    python tools/bench_stream.py --denoise --ab-steps 0 --out profiles/bench_stream_denoise.json
+    python tools/bench_stream.py --formant --ab-steps 0 --out profiles/bench_stream_formant.json"""
 import argparse
 import json
 import os
@@ -61,7 +67,11 @@ def mic_blocks(clips, in_rate, in_channels):
 DN_CASES = {"in": dict(denoise_in={}), "out": dict(denoise_out={}), "both": dict(denoise_in={}, denoise_out={})}
 
 
-def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effects=None, denoise=None):
+FM = dict(semitones=4.0)
+FM_CASES = {"in": dict(formant_in=FM), "out": dict(formant_out=FM), "both": dict(formant_in=FM, formant_out=FM)}
+
+
+def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effects=None, denoise=None, formant=None):
     os.environ["RVCX_STREAM_FULL_SYNTH"] = "1" if full_synth else "0"      # read when the session opens
     p = bench.make_params(seed=1)
     io = io or {}
@@ -69,9 +79,9 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effect
     need = (warmup + steps) * Fb * 160
     clips = np.stack([S.make_clip(100 + s, need / 16000.0 + 0.1)[:need] for s in range(n_streams)]).astype(np.float32)
     clips = mic_blocks(clips, io.get("in_rate", 0), io.get("in_channels", 1))
-    runs, stage_ms, fx_ms, dn_ms = [], [], [], []
+    runs, stage_ms, fx_ms, dn_ms, fm_ms = [], [], [], [], []
     with ctx.stream_open(mid, p, [0] * n_streams, [float(s % 5 - 2) for s in range(n_streams)], Fb, Fc, Fx, Fs, effects=effects,
-                         **io, **(denoise or {})) as se:
+                         **io, **(denoise or {}), **(formant or {})) as se:
         geo = dict(ring_frames=Fc + Fx + Fs + Fb, frames=se.frames, skip_head=se.skip_head, block_in=se.block_in,
                    block_out=se.block_out, in_delay=se.in_delay, out_delay=se.out_delay, latency_ms=round(se.latency_ms, 3))
         for r in range(repeats):
@@ -90,12 +100,14 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effect
                         fx_ms.append(list(se.last_fx_ms().values()))
                     if denoise:
                         dn_ms.append(se.last_dn_ms())
+                    if formant:
+                        fm_ms.append(se.last_fm_ms())
             assert np.isfinite(out).all() and out.any()
             ms = np.asarray(ms)
             runs.append(dict(median_ms=round(float(np.median(ms)), 3), p99_ms=round(float(np.percentile(ms, 99)), 3),
                              max_ms=round(float(ms.max()), 3)))
             print(f"  S={n_streams} full_synth={int(full_synth)} io={io} effects={effects is not None} "
-                  f"denoise={sorted(denoise or {})} run {r}: {runs[-1]}", flush=True)
+                  f"denoise={sorted(denoise or {})} formant={sorted(formant or {})} run {r}: {runs[-1]}", flush=True)
     st = np.median(np.asarray(stage_ms), axis=0)
     res = dict(geometry=geo, runs=runs, median_ms=round(float(np.median([r["median_ms"] for r in runs])), 3),
                p99_ms=round(float(np.max([r["p99_ms"] for r in runs])), 3),
@@ -105,6 +117,8 @@ def run(ctx, mid, n_streams, steps, warmup, repeats, full_synth, io=None, effect
         res["fx_ms_median"] = {n: round(float(v), 4) for n, v in zip(names, np.median(np.asarray(fx_ms), axis=0))}
     if denoise:
         res["dn_ms_median"] = {n: round(float(v), 4) for n, v in zip(("in", "out"), np.median(np.asarray(dn_ms), axis=0))}
+    if formant:
+        res["fm_ms_median"] = {n: round(float(v), 4) for n, v in zip(("in", "out"), np.median(np.asarray(fm_ms), axis=0))}
     return res
 
 
@@ -121,6 +135,7 @@ def main():
     ap.add_argument("--out-rate", type=int, default=0, help="Hz of the blocks a rate session returns (0: the model's rate)")
     ap.add_argument("--no-effects", action="store_true", help="skip the rate session with the effects board inside the step")
     ap.add_argument("--denoise", action="store_true", help="also measure sessions with live noise reduction on either side")
+    ap.add_argument("--formant", action="store_true", help="also measure sessions with the live formant shift on either side")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bench_stream.json"))
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -169,6 +184,18 @@ def main():
                                           plain_median_ms=base["median_ms"],
                                           denoise_costs_ms=round(e["median_ms"] - base["median_ms"], 3),
                                           denoise_costs_device_ms=round(e["stage_ms_median"]["total"]
+                                                                        - base["stage_ms_median"]["total"], 3))
+        if a.formant:     # the same S, model, audio and rates with stage 19 on the input side, the output side and both
+            base = r["rates"] if rates else r
+            r["formant"] = {}
+            for name, fm in FM_CASES.items():
+                e = run(ctx, mid, n_streams, a.steps, a.warmup, a.repeats, False, io if rates else None, formant=fm)
+                r["formant"][name] = dict(geometry=e["geometry"], runs=e["runs"], median_ms=e["median_ms"], p99_ms=e["p99_ms"],
+                                          stage_ms_median=e["stage_ms_median"], fm_ms_median=e["fm_ms_median"],
+                                          real_time_p99=bool(e["p99_ms"] < BLOCK_MS),
+                                          plain_median_ms=base["median_ms"],
+                                          formant_costs_ms=round(e["median_ms"] - base["median_ms"], 3),
+                                          formant_costs_device_ms=round(e["stage_ms_median"]["total"]
                                                                         - base["stage_ms_median"]["total"], 3))
         res["streams"][str(n_streams)] = r
     ok = [int(k) for k, v in res["streams"].items() if v["real_time_p99"]]
